@@ -5,13 +5,33 @@ structured 3D CG1 hexahedral plate of BASELINE.json configs[3] (C4: 50 x 50 x 5
 plate, 400 x 400 x 50 = 8M hex, 8,200,851 temperature dofs).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
 
 One process per GPU (torch.distributed.run sets RANK / LOCAL_RANK /
 WORLD_SIZE); the mesh is sliced along y into N partitions with one ghost node
 plane per interface; RCCL exchanges the ghost planes and all-reduces the PCG /
 Newton dot products.  ``--scaling strong`` (default) partitions the fixed 8M-hex
 mesh; ``weak`` gives every rank its own 400 x 400 x 50 slab of a 400 x 400N x 50
-plate.  Rank 0 prints one JSON line (metric, value, roofline, cpu_baseline ...).
+plate.  Rank 0 prints one JSON line.
+
+A plain run does what the headline figure needs and no more: set up, warm up,
+time the K steps, write the outputs if ``--dump-outputs`` is given, print the
+line (metric, value, unit, ms_per_step, dtype, config ...).  ``--full`` adds the
+measurements that take runs of their own after the timed steps: the isolated
+per-kernel timings and the roofline record (``kernels``, ``roofline``, with the
+committed rocprofv3 / PMC records of profiles/) and the CPU baseline
+(``cpu_baseline``).  The timed steps are the same in both modes.
+
+``--steps`` beyond ``--restart-steps`` (default 200, warm-up included) are timed
+in segments, each on a fresh problem from t = 0 that is set up and warmed up
+outside the timed region: every timed step is one of the transient's first 200
+(see RESTART_STEPS), whatever K is.  The outputs are those of the last segment.
+
+``--dump-outputs DIR`` writes what the last timed step computed, the five
+series a caller of ``solve_timestep`` reads back (T, phi, Tf, xi, sigma), as
+DIR/<name>.npy in float64, straight after the timed steps.  Outputs above the
+size cap are written as a fixed, seeded sample of the dofs (the same dofs for
+every field and every run), so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -29,6 +49,15 @@ for p in (PKG, ROOT):
         sys.path.insert(0, p)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip table)
+# The transient is timed over its first RESTART_STEPS steps only.  Its steps get smaller as the plate
+# cools while the f64 floor of the Newton increment does not (C4: ||dx|| stalls at 2.7e-10, above atol
+# 1e-10), so the reference's incremental criterion (rtol 1e-12 of the step's first increment) takes a
+# fifth iteration from step 273 and cannot be met from step 281 on: the solve raises.  Steps 2-221 of C4
+# all take 4 Newton / 20 Krylov iterations, the cost the short default run has always measured.
+RESTART_STEPS = 200
+DUMP_FIELDS = ("T", "phi", "Tf", "xi", "sigma")  # ThermoViscoProblem.OUTPUT_FIELDS: the reference's five series
+DUMP_MAX_BYTES = 48 * 10**6  # --dump-outputs: all files of one rank together
+DUMP_SEED = 20240229
 
 
 def parse():
@@ -42,7 +71,16 @@ def parse():
     ap.add_argument("--thermal-only", action="store_true")
     ap.add_argument("--family", choices=["CG", "DG"], default="CG",
                     help="element family of T and sigma (degree 1): CG (C1-C4) or DG (C5)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--restart-steps", type=int, default=RESTART_STEPS, metavar="M",
+                    help="time the steps in segments: a fresh problem at t = 0 (set up and warmed up again, untimed) "
+                         "whenever M steps have been taken, warm-up included; 0: one problem for all steps")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the isolated per-kernel timings, the roofline record and "
+                         "the CPU baseline (kernels, roofline, cpu_baseline of the JSON line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the last step's T, phi, Tf, xi and sigma to DIR/<name>.npy "
+                         f"(float64; above {DUMP_MAX_BYTES // 10**6} MB in all a fixed, seeded sample of the dofs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline sample length")
     ap.add_argument("--kernel-reps", type=int, default=20)
     ap.add_argument("--comm", choices=["rccl", "host", "loopback"], default="rccl",
@@ -76,7 +114,10 @@ def parse():
                     help="--share: Newton iterations per step, Krylov iterations per Newton solve")
     ap.add_argument("--pcg", choices=["auto", "kspcg", "single"], default="auto",
                     help="Krylov form: single-reduction (Chronopoulos-Gear, 3D CG) or PETSc KSPCG as written")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps >= 1 and --warmup >= 0")
+    return a
 
 
 def main():
@@ -93,8 +134,6 @@ def main():
         dist.init_process_group("gloo", rank=rank, world_size=world)
 
     from tvfem import box_mesh, distorted_box_mesh
-    from tvfem import _native as N
-    from tvfem.problem import ThermoViscoProblem
 
     nc = [int(v) for v in a.cells.split(",")]
     L = [float(v) for v in a.lengths.split(",")]
@@ -135,12 +174,141 @@ def main():
         nn, kk = (int(v) for v in a.share_its.split(","))
         kw = {"n_parts": a.share, "part": a.share // 2, "part_axis": 1, "newton_fixed_its": nn,
               "ksp_fixed_its": kk}
+    prob = new_problem(a, mesh, cfg, mp, device, pc, kw, rank, world, dist)
+    mg_single = pc == "gmg" and prob.pcg_variant == "single"  # GMG-PCG, Chronopoulos-Gear form (deep-ghost slabs)
+    single = prob.pcg_variant == "single" and not mg_single
+    n_owned, _ = prob.num_dofs(0)
+    n_global = int(np.prod([n + 1 for n in nc])) if a.family == "CG" else 8 * int(np.prod(nc))
+    cname = {("CG", (100, 100, 10)): "C2", ("CG", (200, 200, 25)): "C3", ("CG", (400, 400, 50)): "C4",
+             ("DG", (200, 200, 25)): "C5"}.get((a.family, tuple(nc)), "custom")
+
+    # the timed steps in segments of at most --restart-steps steps since t = 0
+    # (each segment's warm-up included), every segment on a fresh problem
+    seg = max(1, a.restart_steps - a.warmup) if a.restart_steps > 0 else a.steps
+    dt_local, nits, kits, left = 0.0, 0, 0, a.steps
+    while True:
+        n = min(left, seg)
+        dt, ni, ki = run_segment(a, prob, n, dist)
+        dt_local, nits, kits, left = dt_local + dt, nits + ni, kits + ki, left - n
+        if left == 0:
+            break
+        prob.close()  # frees the device state before the next problem allocates its own
+        prob = new_problem(a, mesh, cfg, mp, device, pc, kw, rank, world, dist)
+    lib, ctx = prob._lib, prob._ctx
+    if dist is not None:
+        import torch
+        t = torch.tensor([dt_local], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    else:
+        elapsed = dt_local
+
+    # the last timed step's outputs, before anything else touches the state
+    if a.dump_outputs is not None:
+        if a.share > 1:
+            raise SystemExit("--dump-outputs: a stubbed or loopback share is no solution to read (tv_get_field refuses)")
+        dump_outputs(prob, a.dump_outputs, rank, world)
+
+    kern = roofline = cpu = None
+    if a.full:  # measurements with runs of their own; they reuse (and overwrite) the solver state
+        kern, roofline, cpu = full_records(a, lib, ctx, pc, single, um, nc, L, mp, rank, world)
+
+    prob.close()
+    if rank == 0:
+        value = n_global * a.steps / elapsed
+        out = {
+            "metric": f"DOF-updates/sec ({'thermal Newton' if a.thermal_only else 'coupled thermo-visco'} "
+                      f"time step, 3D {a.family}1 hex)",
+            "value": value,
+            "unit": "DOF-updates/s",
+            "n_gpus": world,
+            "steps": a.steps,
+            "warmup": a.warmup,
+            "restart_steps": a.restart_steps,
+            "ms_per_step": elapsed / a.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": a.scaling,
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic (uniform T_0 = 800 K initial state, main.py parameters)",
+            "config": {"workload": ("distorted-hex " if um else "")
+                                   + f"{cname} 3D plate {a.family}1/{a.family}1 {nc[0]}x{nc[1]}x{nc[2]} hex "
+                                   f"({n_global} T-dofs), dt 0.1, "
+                                   + ("thermal-only" if a.thermal_only else "coupled 6-term Prony"),
+                       "parallelism": (f"ONE rank's share (partition {a.share // 2} of {a.share}, its slab of "
+                                       f"{n_owned} owned T-dofs) on one GPU, "
+                                       + ("the production RCCL groups on a one-rank loopback communicator "
+                                          "(self send/receive pairs; one-rank all-reduces are local copies)"
+                                          if a.comm == "loopback" else "communication stubbed")
+                                       + f", iterations fixed at {a.share_its} (Newton per step, Krylov per solve): "
+                                       "the per-rank step without cross-GPU transfer time, not a multi-GPU "
+                                       "measurement"
+                                       if a.share > 1 else
+                                       "single GPU, one partition (no communication)" if world == 1 else
+                                       (f"RCB cell partition x{world} with a ghost-cell layer ("
+                                        if um else f"mesh partition along y x{world} (")
+                                       + ("RCCL halo + allreduce" if a.comm == "rccl" else "host-staged gloo") + ")"),
+                       "newton_its_per_step": nits / a.steps, "krylov_its_per_step": kits / a.steps,
+                       "output": (f"T, phi, Tf, xi, sigma written every step (async XDMF) to {a.output}"
+                                  if a.output else "none (reference writes VTX/XDMF every step)"),
+                       "krylov_form": ("single-reduction (Chronopoulos-Gear) Jacobi-PCG" if single
+                                       else "PETSc KSPCG Jacobi-PCG" if pc == "jacobi"
+                                       else "PETSc KSPCG, smoothed-aggregation AMG preconditioner (additive "
+                                       "level 0)" if pc == "amg"
+                                       else "single-reduction (Chronopoulos-Gear) CG, geometric-multigrid V-cycle "
+                                       "preconditioner, three ghost planes per slab interface" if mg_single
+                                       else "PETSc KSPCG, geometric-multigrid V-cycle preconditioner"),
+                       "preconditioner": pc,
+                       "visco_fields": "state (T, Tf, Tf_partial, phi, xi, s_tilde, sigma_tilde, sigma)"},
+        }
+        if a.dump_outputs is not None:
+            out["outputs"] = a.dump_outputs
+        if a.full:
+            out.update({"roofline": roofline, "kernels": kern, "cpu_baseline": cpu})
+        print(json.dumps(out))
+
+
+def run_segment(a, prob, n, dist):
+    """Warm up and time n steps of prob; returns this rank's seconds and the Newton / Krylov iterations."""
+    from tvfem import _native as N
+    lib, ctx = prob._lib, prob._ctx
+
+    def barrier_sync():
+        N.check(lib.tv_sync(ctx), ctx)
+        if dist is not None:
+            dist.barrier()
+
+    step = lambda: prob.solve_timestep(thermal_only=a.thermal_only)  # noqa: E731
+    for _ in range(a.warmup):
+        step()
+    barrier_sync()
+    # the hot kernels are timed inside the timed steps themselves: the fused
+    # matvec and the update of every converging PCG iteration write device clock
+    # stamps (first workgroup's start, reduction tail's end), the visco update is
+    # bracketed by HIP events
+    if not a.no_kernel_timing:
+        N.check(lib.tv_kernel_timing(ctx, 1), ctx)
+    t0 = time.perf_counter()
+    nits = kits = 0
+    for _ in range(n):
+        step()
+        nits += prob.last_newton_iterations
+        kits += prob.last_krylov_iterations
+    if a.output is not None:  # the timed region includes draining the writer
+        prob._finalize()
+    barrier_sync()
+    return time.perf_counter() - t0, nits, kits
+
+
+def new_problem(a, mesh, cfg, mp, device, pc, kw, rank, world, dist):
+    """A fresh ThermoViscoProblem of the bench's workload at t = 0, its transport initialised and checked."""
+    from tvfem import _native as N
+    from tvfem.problem import ThermoViscoProblem
+
     prob = ThermoViscoProblem(mesh, (0.0, 50.0), 0.1, cfg, mp, device=device, materialize=False,
                               verbose=False, pcg_variant=a.pcg, preconditioner=pc, mg_levels=a.mg_levels,
                               mg_coupling=a.mg_coupling, dg_tile_chunk=a.dg_tile_chunk,
                               write_output=a.output is not None, output_dir=a.output or "output", **kw)
-    mg_single = pc == "gmg" and prob.pcg_variant == "single"  # GMG-PCG, Chronopoulos-Gear form (deep-ghost slabs)
-    single = prob.pcg_variant == "single" and not mg_single
     lib, ctx = prob._lib, prob._ctx
     if a.share > 1 and a.comm == "loopback":  # the production RCCL groups, self send / receive pairs
         os.environ.setdefault("NCCL_SOCKET_IFNAME", "lo")
@@ -171,43 +339,33 @@ def main():
                   f"{lib.tv_last_error(ctx)}", file=sys.stderr, flush=True)
             raise SystemExit(3)
     prob.setup()
-    n_owned, _ = prob.num_dofs(0)
-    n_global = int(np.prod([n + 1 for n in nc])) if a.family == "CG" else 8 * int(np.prod(nc))
-    cname = {("CG", (100, 100, 10)): "C2", ("CG", (200, 200, 25)): "C3", ("CG", (400, 400, 50)): "C4",
-             ("DG", (200, 200, 25)): "C5"}.get((a.family, tuple(nc)), "custom")
+    return prob
 
-    def barrier_sync():
-        N.check(lib.tv_sync(ctx), ctx)
-        if dist is not None:
-            dist.barrier()
 
-    step = lambda: prob.solve_timestep(thermal_only=a.thermal_only)  # noqa: E731
-    for _ in range(a.warmup):
-        step()
-    barrier_sync()
-    # the hot kernels are timed inside the timed steps themselves: the fused
-    # matvec and the update of every converging PCG iteration write device clock
-    # stamps (first workgroup's start, reduction tail's end), the visco update is
-    # bracketed by HIP events
-    if not a.no_kernel_timing:
-        N.check(lib.tv_kernel_timing(ctx, 1), ctx)
-    t0 = time.perf_counter()
-    nits = kits = 0
-    for _ in range(a.steps):
-        step()
-        nits += prob.last_newton_iterations
-        kits += prob.last_krylov_iterations
-    if a.output is not None:  # the timed region includes draining the writer
-        prob._finalize()
-    barrier_sync()
-    dt_local = time.perf_counter() - t0
-    if dist is not None:
-        import torch
-        t = torch.tensor([dt_local], dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    else:
-        elapsed = dt_local
+def dump_outputs(prob, out_dir, rank, world):
+    """--dump-outputs: the five series of the step just taken as DIR/<name>.npy
+    (float64, the reference's interleaved layout reshaped to (dofs, block));
+    DIR/<name>_part<rank>.npy when partitioned.  Above DUMP_MAX_BYTES in all,
+    the same seeded sample of the dofs (sorted, without replacement) of every
+    field."""
+    os.makedirs(out_dir, exist_ok=True)
+    bs = {f: prob._bs[f] for f in DUMP_FIELDS}
+    n = prob.num_dofs(0)[0]
+    if any(prob.num_dofs(1 if f == "sigma" else 0)[0] != n for f in DUMP_FIELDS):
+        raise SystemExit("--dump-outputs: T and sigma spaces of different size")
+    keep = DUMP_MAX_BYTES // (8 * sum(bs.values()))
+    idx = None
+    if n > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+    for f in DUMP_FIELDS:
+        v = prob.get_field(f).reshape(n, bs[f])
+        v = np.ascontiguousarray(v if idx is None else v[idx], dtype=np.float64)
+        np.save(os.path.join(out_dir, f + (f"_part{rank}" if world > 1 else "") + ".npy"), v)
+
+
+def full_records(a, lib, ctx, pc, single, um, nc, L, mp, rank, world):
+    """--full: the records measured after the timed steps (kernels, roofline, cpu_baseline)."""
+    from tvfem import _native as N
 
     # ---- per-kernel timing and algorithmic bytes ----
     # "ms": mean launch duration inside the timed steps (device clock stamps of
@@ -275,7 +433,7 @@ def main():
                                          f"{pf['launches']} flushed launches: " + os.path.relpath(prof_file, ROOT))
     dom = kern[names[0] if um else names[3]]
     # traffic: HBM bytes per launch of this kernel from the rocprofv3 --pmc passes
-    # (FETCH_SIZE x 2 + WRITE_SIZE, MI355X_MICROARCH.md HBM section) of this same
+    # (FETCH_SIZE x 2 + WRITE_SIZE) of this same
     # bench command, committed under profiles/ (counters cannot be read inside
     # the timed run); traffic_source names the file
     traffic, traffic_src = None, None
@@ -330,58 +488,7 @@ def main():
                    "sample": "no unstructured path in oracle/tv_cpu.c (the numpy oracle covers its parity only)"}
         else:
             cpu = cpu_baseline(nc, L, mp, a.cpu_seconds, a.thermal_only, a.family, pc)
-
-    prob.close()
-    if rank == 0:
-        value = n_global * a.steps / elapsed
-        out = {
-            "metric": f"DOF-updates/sec ({'thermal Newton' if a.thermal_only else 'coupled thermo-visco'} "
-                      f"time step, 3D {a.family}1 hex)",
-            "value": value,
-            "unit": "DOF-updates/s",
-            "n_gpus": world,
-            "steps": a.steps,
-            "warmup": a.warmup,
-            "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": a.scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic (uniform T_0 = 800 K initial state, main.py parameters)",
-            "config": {"workload": ("distorted-hex " if um else "")
-                                   + f"{cname} 3D plate {a.family}1/{a.family}1 {nc[0]}x{nc[1]}x{nc[2]} hex "
-                                   f"({n_global} T-dofs), dt 0.1, "
-                                   + ("thermal-only" if a.thermal_only else "coupled 6-term Prony"),
-                       "parallelism": (f"ONE rank's share (partition {a.share // 2} of {a.share}, its slab of "
-                                       f"{n_owned} owned T-dofs) on one GPU, "
-                                       + ("the production RCCL groups on a one-rank loopback communicator "
-                                          "(self send/receive pairs; one-rank all-reduces are local copies)"
-                                          if a.comm == "loopback" else "communication stubbed")
-                                       + f", iterations fixed at {a.share_its} (Newton per step, Krylov per solve): "
-                                       "the per-rank step without cross-GPU transfer time, not a multi-GPU "
-                                       "measurement"
-                                       if a.share > 1 else
-                                       "single GPU, one partition (no communication)" if world == 1 else
-                                       (f"RCB cell partition x{world} with a ghost-cell layer ("
-                                        if um else f"mesh partition along y x{world} (")
-                                       + ("RCCL halo + allreduce" if a.comm == "rccl" else "host-staged gloo") + ")"),
-                       "newton_its_per_step": nits / a.steps, "krylov_its_per_step": kits / a.steps,
-                       "output": (f"T, phi, Tf, xi, sigma written every step (async XDMF) to {a.output}"
-                                  if a.output else "none (reference writes VTX/XDMF every step)"),
-                       "krylov_form": ("single-reduction (Chronopoulos-Gear) Jacobi-PCG" if single
-                                       else "PETSc KSPCG Jacobi-PCG" if pc == "jacobi"
-                                       else "PETSc KSPCG, smoothed-aggregation AMG preconditioner (additive "
-                                       "level 0)" if pc == "amg"
-                                       else "single-reduction (Chronopoulos-Gear) CG, geometric-multigrid V-cycle "
-                                       "preconditioner, three ghost planes per slab interface" if mg_single
-                                       else "PETSc KSPCG, geometric-multigrid V-cycle preconditioner"),
-                       "preconditioner": pc,
-                       "visco_fields": "state (T, Tf, Tf_partial, phi, xi, s_tilde, sigma_tilde, sigma)"},
-            "roofline": roofline,
-            "kernels": kern,
-            "cpu_baseline": cpu,
-        }
-        print(json.dumps(out))
+    return kern, roofline, cpu
 
 
 class _StdoutToStderr:

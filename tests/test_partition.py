@@ -371,14 +371,16 @@ def test_rccl_partitioned_run_matches_single_partition(world):
 @pytest.mark.gpu
 def test_bench_two_rank_rehearsal():
     """bench.py's distributed flow (barriers, max-over-ranks timing, rank-0 JSON
-    line) at world size 2 with the host-staged transport, both ranks on GPU 0."""
+    line) at world size 2 with the host-staged transport, both ranks on GPU 0;
+    the two timed steps as two segments (--restart-steps 2 with one warm-up step),
+    so the second problem's transport is initialised and checked as well."""
     import torch
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", "29711", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--comm", "host", "--cells", "40,40,10", "--steps", "2", "--warmup", "1",
-           "--kernel-reps", "2", "--no-cpu-baseline"]
+           "--full", "--kernel-reps", "2", "--no-cpu-baseline", "--restart-steps", "2"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

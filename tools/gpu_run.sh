@@ -35,7 +35,7 @@ EOF
 run_bench() {  # tag, lib suffix, args...
   local tag=$1 v=$2; shift 2
   local o=$OUT/bench_${tag}${v:+_$v}
-  TVFEM_LIB=$PWD/fem-glass-tempering_amd/tvfem/libtvfem$v.so timeout -k 10 600 python3 bench.py "$@" > $o.json 2> $o.err ||
+  TVFEM_LIB=$PWD/fem-glass-tempering_amd/tvfem/libtvfem$v.so timeout -k 10 600 python3 bench.py --full "$@" > $o.json 2> $o.err ||
     { tail -5 $o.err; return 1; }
   line $o.json "${tag}${v:+ lib$v}"
 }
@@ -64,7 +64,7 @@ for MODE in "$@"; do
         step "trace $tag"
         mkdir -p $OUT/tr_$tag
         timeout -k 10 400 rocprofv3 --kernel-trace -d $OUT/tr_$tag/prof -o run --output-format csv -- \
-          python3 bench.py --no-cpu-baseline "${argv[@]}" > $OUT/tr_$tag/b.json 2> $OUT/tr_$tag/b.err ||
+          python3 bench.py --full --no-cpu-baseline "${argv[@]}" > $OUT/tr_$tag/b.json 2> $OUT/tr_$tag/b.err ||
           { tail -5 $OUT/tr_$tag/b.err; exit 1; }
         f=$(find $OUT/tr_$tag/prof -name "run_kernel_trace.csv" | head -1)
         mv "$f" $OUT/tr_$tag/run_kernel_trace.csv
@@ -76,7 +76,7 @@ for MODE in "$@"; do
     stats)
       step "C4 bench under rocprofv3 --kernel-trace --stats"
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_bench -o run --output-format csv -- \
-        python3 bench.py --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err || { tail -5 $OUT/bench_prof.err; exit 1; }
+        python3 bench.py --full --no-cpu-baseline > $OUT/bench_prof.json 2> $OUT/bench_prof.err || { tail -5 $OUT/bench_prof.err; exit 1; }
       python3 tools/profile_summary.py $OUT/prof_bench $OUT/bench_prof.json $OUT/profile_summary.json > $OUT/profile_summary.log 2>&1
       line $OUT/bench_prof.json C4prof
       ;;

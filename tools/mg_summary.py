@@ -1,4 +1,4 @@
-"""Summarise a gpu_mg.sh run: bench line and per-(kernel, grid size) trace means."""
+"""Summarise a gpu_mg.sh run: bench line (of bench.py --full) and per-(kernel, grid size) trace means."""
 import collections
 import csv
 import json

@@ -3,6 +3,8 @@ trace of the same command:
 
     python tools/profile_summary.py PROF_DIR BENCH_JSON OUT_JSON
 
+(BENCH_JSON: the line of ``bench.py --full`` run under the trace.)
+
 For each hot kernel: the rocprofv3 mean over all dispatches, and the mean over
 the dispatches of bench.py's timed steps that do work.  The timed steps are
 located by the visco update launches (one per step: `warmup` of them precede

@@ -2,6 +2,8 @@
 single-GPU problems, no halo or allreduce) and the C2-C5 lines into one record.
 
     python tools/strong_shapes.py OUT.json tag=bench.json [tag=bench.json ...]
+
+The bench lines are those of ``bench.py --full`` (they carry the ``kernels`` record).
 """
 import json
 import sys
@@ -16,7 +18,7 @@ def main():
                     "krylov_its_per_step": d["config"]["krylov_its_per_step"],
                     "workload": d["config"]["workload"],
                     "kernels_us": {k: round(v["ms"] * 1e3, 2) for k, v in d["kernels"].items()}}
-    rec = {"source": "bench.py on one MI355X, --steps 10 --no-cpu-baseline (C5: --steps 5); the n*_share shapes "
+    rec = {"source": "bench.py on one MI355X, --full --steps 10 --no-cpu-baseline (C5: --steps 5); the n*_share shapes "
                      "are the per-rank slabs of C4 under strong scaling along y, run as single-GPU problems "
                      "(no halo or allreduce)",
            "runs": out}
