@@ -637,7 +637,10 @@ int tv_abi_version(void) { return TV_ABI_VERSION; }
 
 
 const char* tv_last_error(const void* ctx) {
-  if (ctx) return static_cast<const Ctx*>(ctx)->err.c_str();
+  if (ctx) {
+    if (const char* e = ensemble_last_error(ctx)) return e;  // an ensemble handle (tv_ensemble.cpp)
+    return static_cast<const Ctx*>(ctx)->err.c_str();
+  }
   std::lock_guard<std::mutex> lk(g_err_mu);
   return g_err.c_str();
 }

@@ -9,6 +9,7 @@
 //                   Dirichlet lifting, the viscoelastic step, the operators
 //   tv_mgsolve.cpp  geometric-multigrid hierarchy and the preconditioned solve
 //   tv_measure.cpp  in-solve kernel timing, algorithmic bytes, timed launches
+//   tv_ensemble.cpp ensembles of 1D bars (its own handle, not a Ctx)
 //
 // Reference mapping (file:line under /root/reference):
 //   Ctx construction      ThermoViscoProblem.__init__ (ThermoViscoProblem.py:24-58)
@@ -294,6 +295,8 @@ double amg_cycle_bytes(const Ctx* c);
 
 // ---- tv_context.cpp ----
 void set_global_error(const std::string& m);
+// the error text of a live ensemble handle (tv_ensemble.cpp), nullptr for any other pointer
+const char* ensemble_last_error(const void* handle);
 void axis_coefs(const std::vector<double>& X, int first, int count, std::vector<double>& out);
 const std::vector<double>& storage_coords(Ctx* c, int s, std::vector<double>& tmp);
 bool storage_perm(const tv_mesh_desc* m, int perm[3]);

@@ -1,0 +1,341 @@
+// Ensembles of independent 1D CG1 bars (parameter studies of the reference's
+// own main.py workload): host side of csrc/tv_ensemble.hip.  C-ABI:
+// include/tvfem.h, tv_ensemble_*.
+//   tv_ensemble_create                 ThermoViscoProblem.__init__ once per bar
+//   tv_ensemble_set_initial_condition  _set_initial_condition (:187-233), each bar's T_0
+//   tv_ensemble_step                   n_steps x solve_timestep (:367-381) minus the
+//                                      file output, every bar, one launch per
+//                                      kMaxNodeStepsPerLaunch of work
+#include <set>
+
+#include "tv_ctx.h"
+
+namespace tv {
+
+// Upper bound of n_steps x n_nodes per launch.  A lane spends about 3 us per
+// node and step (measured: 2.9 us on the 49-node main.py bar, three Newton
+// iterations of two dependent sweeps plus the viscoelastic update, mostly
+// memory latency, the same from 64 to 16384 bars), so one launch stays below
+// half a second, far from any watchdog, while a 500-step main.py run of a
+// bar of up to 262 nodes is still a single launch.
+constexpr int64_t kMaxNodeStepsPerLaunch = 1 << 17;
+
+struct Ens {
+  std::string err;
+  int device = 0;
+  hipStream_t stream = nullptr;
+  tv_options O{};
+  EnsArgs a{};
+  ViscoConst vc{};
+  ViscoFields vf{};
+  std::vector<double> T0;     // per bar
+  std::vector<void*> bufs;    // every device allocation
+  double* field[TV_NUM_FIELDS] = {};
+  int bs[TV_NUM_FIELDS] = {};
+  int steps_done = 0;
+  int fail(int code, const std::string& m) {
+    err = m;
+    return code;
+  }
+};
+
+static std::mutex g_ens_mu;
+static std::set<const void*> g_ens_live;  // routes tv_last_error
+
+const char* ensemble_last_error(const void* h) {
+  std::lock_guard<std::mutex> lk(g_ens_mu);
+  if (!g_ens_live.count(h)) return nullptr;
+  return static_cast<const Ens*>(h)->err.c_str();
+}
+
+namespace {
+
+int ens_alloc(Ens* c, size_t bytes, void** out) {
+  HIPC(hipMalloc(out, bytes));
+  c->bufs.push_back(*out);
+  HIPC(hipMemsetAsync(*out, 0, bytes, c->stream));
+  return TV_OK;
+}
+
+int ens_alloc_field(Ens* c, int id, int bs) {
+  void* p = nullptr;
+  if (int e = ens_alloc(c, sizeof(double) * (size_t)bs * c->a.n_nodes * c->a.nb_pad, &p)) return e;
+  c->field[id] = static_cast<double*>(p);
+  c->bs[id] = bs;
+  return TV_OK;
+}
+
+// host [bar][node * bs + comp]  <->  device [comp][node][bar]
+int ens_transfer(Ens* c, int field, double* host, size_t n_values, bool to_device) {
+  if (field < 0 || field >= TV_NUM_FIELDS || !c->field[field])
+    return c->fail(TV_ERR_STATE, "tv_ensemble: field " + std::to_string(field) + " is not part of an ensemble's state");
+  const int bs = c->bs[field], n = c->a.n_nodes, nb = c->a.n_bars;
+  const int64_t pad = c->a.nb_pad;
+  if (!host || n_values != (size_t)nb * n * bs) return c->fail(TV_ERR_ARG, "tv_ensemble: field size mismatch");
+  std::vector<double> dev((size_t)bs * n * pad);
+  const size_t bytes = dev.size() * sizeof(double);
+  HIPC(hipMemcpyAsync(dev.data(), c->field[field], bytes, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  for (int b = 0; b < nb; ++b)
+    for (int i = 0; i < n; ++i)
+      for (int q = 0; q < bs; ++q) {
+        double& d = dev[((size_t)q * n + i) * pad + b];
+        double& h = host[((size_t)b * n + i) * bs + q];
+        if (to_device) d = h;
+        else h = d;
+      }
+  if (to_device) {
+    HIPC(hipMemcpyAsync(c->field[field], dev.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+  }
+  return TV_OK;
+}
+
+}  // namespace
+}  // namespace tv
+
+using namespace tv;
+
+extern "C" {
+
+int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P, const tv_options* opts,
+                       int device, void** ens_out) {
+  if (!d || !fe || !P || !ens_out) {
+    set_global_error("tv_ensemble_create: null argument");
+    return TV_ERR_ARG;
+  }
+  *ens_out = nullptr;
+  auto bad = [](const std::string& m) {
+    set_global_error("tv_ensemble_create: " + m);
+    return TV_ERR_ARG;
+  };
+  if (d->n_bars < 1) return bad("n_bars must be at least 1");
+  if (d->n_cells < 1) return bad("n_cells must be at least 1");
+  if (!d->coords) return bad("coords is null");
+  if (fe->T_family != TV_CG || fe->sigma_family != TV_CG || fe->T_degree != 1 || fe->sigma_degree != 1)
+    return bad("only CG1 temperature with CG1 stress is implemented (DG temperature is out of scope)");
+  auto c = std::make_unique<Ens>();
+  if (opts) c->O = *opts;
+  else tv_default_options(&c->O);
+  if (c->O.model_mode != TV_MODEL_REFERENCE) return bad("model_mode PAPER is not implemented for ensembles");
+  if (!(P->dt > 0.0)) return bad("dt must be positive");
+  if (c->O.newton_max_it < 1 || c->O.newton_rtol < 0.0 || c->O.newton_atol < 0.0)
+    return bad("newton_max_it < 1 or a negative Newton tolerance");
+  const int nb = d->n_bars, n = d->n_cells + 1;
+  for (int b = 0; b < (d->coords_shared ? 1 : nb); ++b) {
+    const double* X = d->coords + (size_t)b * n;
+    for (int i = 0; i + 1 < n; ++i)
+      if (!(X[i + 1] > X[i])) return bad("coordinates of bar " + std::to_string(b) + " are not strictly increasing");
+  }
+  const int64_t pad = ((int64_t)nb + kWave - 1) / kWave * kWave;
+  if (pad * n * 6 > INT64_C(1) << 40 || pad > INT32_MAX) return bad("ensemble too large");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    set_global_error("no HIP device available: libtvfem requires an MI355X (gfx950) GPU");
+    return TV_ERR_HIP;
+  }
+  if (device < 0 || device >= ndev) return bad("device index out of range");
+  c->device = device;
+  if (hipSetDevice(device) != hipSuccess ||
+      hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+    set_global_error("HIP stream creation failed");
+    return TV_ERR_HIP;
+  }
+  EnsArgs& a = c->a;
+  a.n_bars = nb;
+  a.nb_pad = (int)pad;
+  a.n_nodes = n;
+  a.max_it = c->O.newton_max_it;
+  a.rtol = c->O.newton_rtol;
+  a.atol = c->O.newton_atol;
+  a.dt = P->dt;
+  a.sigma_sb = P->sigma;
+  // per-bar parameters and cell coefficients, bar-fastest; padding lanes hold zeros (never read)
+  auto per_bar = [&](const double* v, double dflt, int b) { return v ? v[b] : dflt; };
+  std::vector<double> par((size_t)4 * pad, 0.0), cell((size_t)2 * (n - 1) * pad, 0.0);
+  c->T0.resize(nb);
+  for (int b = 0; b < nb; ++b) {
+    par[b] = per_bar(d->htc, P->htc, b);
+    par[pad + b] = per_bar(d->T_ambient, P->T_ambient, b);
+    par[2 * pad + b] = per_bar(d->epsilon, P->epsilon, b);
+    par[3 * pad + b] = per_bar(d->f, P->f, b);
+    c->T0[b] = per_bar(d->T_0, P->T_0, b);
+    const double alpha = per_bar(d->alpha, P->alpha, b);
+    const double* X = d->coords + (d->coords_shared ? 0 : (size_t)b * n);
+    for (int i = 0; i + 1 < n; ++i) {
+      const double h = X[i + 1] - X[i];
+      cell[(size_t)i * pad + b] = h / 6.0;
+      cell[((size_t)(n - 1) + i) * pad + b] = P->dt * alpha / h;
+    }
+  }
+  int rc = TV_OK;
+  void *dpar = nullptr, *dcell = nullptr, *scr = nullptr, *its = nullptr, *fs = nullptr, *tot = nullptr;
+  static const int kState[][2] = {{TV_F_T, 1}, {TV_F_T_PREV, 1}, {TV_F_TF, 1}, {TV_F_TF_PARTIAL, 6}, {TV_F_PHI, 1},
+                                  {TV_F_XI, 1}, {TV_F_SIGMA, 1}, {TV_F_S_TILDE, 6}, {TV_F_SIGMA_TILDE, 6}};
+  for (const auto& s : kState)
+    if (rc == TV_OK) rc = ens_alloc_field(c.get(), s[0], s[1]);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), par.size() * sizeof(double), &dpar);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), cell.size() * sizeof(double), &dcell);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(double) * 2 * n * pad, &scr);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &its);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &fs);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int64_t) * pad, &tot);
+  auto upload = [&](void* dst, const std::vector<double>& src) {
+    HIPC(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    return (int)TV_OK;
+  };
+  if (rc == TV_OK) rc = upload(dpar, par);
+  if (rc == TV_OK) rc = upload(dcell, cell);
+  if (rc != TV_OK) {
+    set_global_error(c->err);
+    for (void* p : c->bufs) hipFree(p);
+    hipStreamDestroy(c->stream);
+    return rc;
+  }
+  double* dp = static_cast<double*>(dpar);
+  a.htc = dp;
+  a.T_amb = dp + pad;
+  a.eps = dp + 2 * pad;
+  a.f = dp + 3 * pad;
+  a.cm = static_cast<double*>(dcell);
+  a.ck = a.cm + (size_t)(n - 1) * pad;
+  a.T = c->field[TV_F_T];
+  a.Tp = c->field[TV_F_T_PREV];
+  a.scr = static_cast<double*>(scr);
+  a.its_last = static_cast<int*>(its);
+  a.failed_step = static_cast<int*>(fs);
+  a.newton_total = static_cast<int64_t*>(tot);
+  // the shared viscoelastic constants, as visco_setup (tv_solver.cpp) forms them
+  ViscoConst& k = c->vc;
+  k.H_over_Rg = P->H / P->Rg;
+  k.inv_Tb = 1.0 / P->Tb;
+  k.dt = P->dt;
+  k.half_dt = P->dt / 2;
+  k.alpha_s = P->alpha_solid;
+  k.dalpha = P->alpha_liquid - P->alpha_solid;
+  k.inv_dim = 1.0;
+  k.chi = 0.5;
+  k.paper = 0;
+  for (int i = 0; i < 6; ++i) {
+    k.lambda_m[i] = P->lambda_m[i]; k.m_n[i] = P->m_n[i];
+    k.lambda_g[i] = P->lambda_g[i]; k.g_n[i] = P->g_n[i];
+    k.lambda_k[i] = P->lambda_k[i]; k.k_n[i] = P->k_n[i];
+  }
+  ViscoFields& v = c->vf;
+  std::memset(&v, 0, sizeof(v));
+  v.sT = v.sS = (int64_t)n * pad;
+  v.T = c->field[TV_F_T]; v.Tp = c->field[TV_F_T_PREV];
+  v.phi = c->field[TV_F_PHI]; v.xi = c->field[TV_F_XI];
+  v.Tf = c->field[TV_F_TF]; v.Tfp = c->field[TV_F_TF_PARTIAL];
+  v.st = c->field[TV_F_S_TILDE]; v.sgt = c->field[TV_F_SIGMA_TILDE];
+  v.sigma = c->field[TV_F_SIGMA];
+  {
+    std::lock_guard<std::mutex> lk(g_ens_mu);
+    g_ens_live.insert(c.get());
+  }
+  *ens_out = c.release();
+  return TV_OK;
+}
+
+
+int tv_ensemble_destroy(void* ens) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  {
+    std::lock_guard<std::mutex> lk(g_ens_mu);
+    if (!g_ens_live.erase(c)) return TV_ERR_ARG;
+  }
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);
+  for (void* p : c->bufs) hipFree(p);
+  hipStreamDestroy(c->stream);
+  delete c;
+  return TV_OK;
+}
+
+
+int tv_ensemble_set_initial_condition(void* ens) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  // __set_IC_T, __set_IC_Tf, __set_IC_Tf_partial (ThermoViscoProblem.py:193-233) with each bar's T_0
+  const int n = c->a.n_nodes;
+  const int64_t pad = c->a.nb_pad;
+  std::vector<double> v((size_t)6 * n * pad, 0.0);
+  for (int q = 0; q < 6 * n; ++q)
+    for (int b = 0; b < c->a.n_bars; ++b) v[(size_t)q * pad + b] = c->T0[b];
+  const size_t plane = sizeof(double) * n * pad;
+  HIPC(hipMemcpyAsync(c->field[TV_F_T], v.data(), plane, hipMemcpyHostToDevice, c->stream));
+  HIPC(hipMemcpyAsync(c->field[TV_F_T_PREV], v.data(), plane, hipMemcpyHostToDevice, c->stream));
+  HIPC(hipMemcpyAsync(c->field[TV_F_TF], v.data(), plane, hipMemcpyHostToDevice, c->stream));
+  HIPC(hipMemcpyAsync(c->field[TV_F_TF_PARTIAL], v.data(), 6 * plane, hipMemcpyHostToDevice, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  return TV_OK;
+}
+
+
+int tv_ensemble_step(void* ens, int n_steps, int thermal_only) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  if (n_steps < 0 || (int64_t)c->steps_done + n_steps > INT32_MAX - 1)
+    return c->fail(TV_ERR_ARG, "tv_ensemble_step: n_steps out of range");
+  hipSetDevice(c->device);
+  const int before = c->steps_done;
+  const int per_launch = (int)std::max<int64_t>(1, kMaxNodeStepsPerLaunch / c->a.n_nodes);
+  for (int left = n_steps; left > 0;) {
+    EnsArgs a = c->a;
+    a.n_steps = std::min(left, per_launch);
+    a.step_base = c->steps_done;
+    a.thermal_only = thermal_only ? 1 : 0;
+    launch_ensemble(a, c->vc, c->vf, c->stream);
+    HIPC(hipGetLastError());
+    c->steps_done += a.n_steps;
+    left -= a.n_steps;
+  }
+  // the failure records decide the status: wait for the launches
+  std::vector<int> failed(c->a.n_bars);
+  HIPC(hipMemcpyAsync(failed.data(), c->a.failed_step, sizeof(int) * failed.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  if (!c->O.error_on_nonconvergence) return TV_OK;
+  for (int b = 0; b < c->a.n_bars; ++b)
+    if (failed[b] > before)
+      return c->fail(TV_ERR_NOT_CONVERGED,
+                     "Newton solver did not converge because maximum number of iterations reached: bar " +
+                         std::to_string(b) + " at step " + std::to_string(failed[b]) + " (first failed bar; frozen)");
+  return TV_OK;
+}
+
+
+int tv_ensemble_get_field(void* ens, int field, double* host, size_t n_values) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  return ens_transfer(c, field, host, n_values, false);
+}
+
+
+int tv_ensemble_set_field(void* ens, int field, const double* host, size_t n_values) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  return ens_transfer(c, field, const_cast<double*>(host), n_values, true);
+}
+
+
+int tv_ensemble_stats(void* ens, int* newton_its_last, int* failed_step, int64_t* newton_total) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  const size_t nb = c->a.n_bars;
+  if (newton_its_last)
+    HIPC(hipMemcpyAsync(newton_its_last, c->a.its_last, sizeof(int) * nb, hipMemcpyDeviceToHost, c->stream));
+  if (failed_step)
+    HIPC(hipMemcpyAsync(failed_step, c->a.failed_step, sizeof(int) * nb, hipMemcpyDeviceToHost, c->stream));
+  if (newton_total)
+    HIPC(hipMemcpyAsync(newton_total, c->a.newton_total, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  return TV_OK;
+}
+
+}  // extern "C"

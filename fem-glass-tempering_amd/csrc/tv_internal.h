@@ -393,6 +393,35 @@ void launch_visco(int dim, int all, const ViscoConst& c, const ViscoFields& f, h
 void launch_visco_Tpass(int dim, int all, const ViscoConst& c, const ViscoFields& f, hipStream_t s);
 void launch_visco_Spass(int dim, int all, const ViscoConst& c, const ViscoFields& f, hipStream_t s);
 
+// ---- ensemble of independent 1D CG1 bars (tv_ensemble.hip) ----
+// One lane per bar; every per-bar array is bar-fastest, [component][node][bar]
+// with the bar count padded to a multiple of the wavefront (nb_pad), so element
+// (node i, bar b) of a field is i * nb_pad + b and a wave's loads and stores
+// are contiguous 512-byte segments.  The ViscoFields passed with it use the
+// same indexing (component stride = n_nodes * nb_pad).
+struct EnsArgs {
+  int n_bars, nb_pad, n_nodes;
+  int n_steps;                // time steps of this launch
+  int step_base;              // steps completed before this launch (failed_step is 1-based)
+  int thermal_only;
+  int max_it;
+  double rtol, atol;          // dolfinx incremental Newton test
+  double dt, sigma_sb;
+  const double* cm;           // [n_nodes - 1][nb_pad] h / 6 per cell
+  const double* ck;           // [n_nodes - 1][nb_pad] dt alpha / h per cell
+  const double* htc;          // [nb_pad] per-bar parameters
+  const double* T_amb;
+  const double* eps;
+  const double* f;
+  double* T;                  // [n_nodes][nb_pad]
+  double* Tp;
+  double* scr;                // Thomas scratch: [2][n_nodes][nb_pad] (modified upper diagonal, right-hand side)
+  int* its_last;              // [nb_pad] Newton iterations of the bar's last solve
+  int* failed_step;           // [nb_pad] 0, or the step at which the bar failed (frozen from then on)
+  int64_t* newton_total;      // [nb_pad]
+};
+void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, hipStream_t s);
+
 // PCG vector kernels over the owned range [0, n) of already-offset pointers
 constexpr int kVecBlocks = 1024;        // grid cap of the vector kernels
 constexpr int kVecBlocksMin = 256;      // below this the grid no longer shrinks with n

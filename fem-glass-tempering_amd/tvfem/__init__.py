@@ -8,6 +8,7 @@ creating a problem requires the built library and an MI355X GPU.
 """
 from .mesh import RectilinearMesh, UnstructuredMesh, box_mesh, distorted_box_mesh, interval_mesh, read_msh  # noqa: F401
 from ._native import lib_path, load_library, NativeError  # noqa: F401
+from .ensemble import ThermoViscoEnsemble  # noqa: F401
 
-__all__ = ["RectilinearMesh", "UnstructuredMesh", "box_mesh", "distorted_box_mesh", "interval_mesh", "read_msh", "lib_path", "load_library",
+__all__ = ["ThermoViscoEnsemble","RectilinearMesh", "UnstructuredMesh", "box_mesh", "distorted_box_mesh", "interval_mesh", "read_msh", "lib_path", "load_library",
            "NativeError"]

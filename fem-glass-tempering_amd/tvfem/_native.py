@@ -41,6 +41,8 @@ EXPORTS = [
     "tv_set_dirichlet", "tv_get_options", "tv_set_newton_tolerances", "tv_set_ksp_tolerances",
     "tv_output_open", "tv_output_open_named", "tv_output_write", "tv_output_close", "tv_xdmf_open",
     "tv_xdmf_add_field", "tv_xdmf_append", "tv_xdmf_close",
+    "tv_ensemble_create", "tv_ensemble_destroy", "tv_ensemble_set_initial_condition", "tv_ensemble_step",
+    "tv_ensemble_get_field", "tv_ensemble_set_field", "tv_ensemble_stats",
 ]
 
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
@@ -69,6 +71,12 @@ class UPartDesc(C.Structure):
                 ("global_offset", C.c_int64), ("n_neighbors", C.c_int), ("neighbors", C.POINTER(C.c_int)),
                 ("recv_count", C.POINTER(C.c_int64)), ("send_count", C.POINTER(C.c_int64)),
                 ("send_idx", C.POINTER(C.c_int64))]
+
+
+class EnsembleDesc(C.Structure):
+    _fields_ = ([("n_bars", C.c_int), ("n_cells", C.c_int), ("coords", C.POINTER(C.c_double)),
+                 ("coords_shared", C.c_int)]
+                + [(n, C.POINTER(C.c_double)) for n in ("htc", "T_0", "T_ambient", "epsilon", "alpha", "f")])
 
 
 class FeConfig(C.Structure):
@@ -175,6 +183,14 @@ def load_library():
         "tv_xdmf_add_field": (C.c_int, [vp, C.c_char_p, C.c_int, C.c_int]),
         "tv_xdmf_append": (C.c_int, [vp, C.c_int, C.c_double, dp, C.c_size_t]),
         "tv_xdmf_close": (None, [vp]),
+        "tv_ensemble_create": (C.c_int, [C.POINTER(EnsembleDesc), C.POINTER(FeConfig), C.POINTER(Params),
+                                         C.POINTER(Options), C.c_int, C.POINTER(vp)]),
+        "tv_ensemble_destroy": (C.c_int, [vp]),
+        "tv_ensemble_set_initial_condition": (C.c_int, [vp]),
+        "tv_ensemble_step": (C.c_int, [vp, C.c_int, C.c_int]),
+        "tv_ensemble_get_field": (C.c_int, [vp, C.c_int, dp, C.c_size_t]),
+        "tv_ensemble_set_field": (C.c_int, [vp, C.c_int, dp, C.c_size_t]),
+        "tv_ensemble_stats": (C.c_int, [vp, ip, ip, i64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

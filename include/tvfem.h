@@ -58,7 +58,8 @@ extern "C" {
                             6: tv_comm_time;
                             7: tv_get_options, tv_set_newton_tolerances, tv_set_ksp_tolerances,
                                tv_last_converged;
-                            8: tv_options lost the unused use_graphs field */
+                            8: tv_options lost the unused use_graphs field;
+                               (still 8, additions only: tv_ensemble_desc and the tv_ensemble_* functions) */
 
 /* status codes */
 #define TV_OK 0
@@ -387,6 +388,51 @@ int tv_visco_update(void* ctx);
  * (tv_last_converged tells; the reference's _solve_T would then fail its
  * assert(converged), ThermoViscoProblem.py:390) */
 int tv_step(void* ctx, int thermal_only, int* newton_its, int* krylov_its);
+
+/* ---- ensembles of independent 1D bars ---------------------------------------
+ * A parameter study of the reference's own workload (main.py: one
+ * through-thickness bar): n_bars bars with the same cell count, each with its
+ * own node coordinates, htc, T_0, T_ambient, epsilon, alpha and f; dt, the
+ * Stefan-Boltzmann sigma and every viscoelastic constant are shared
+ * (tv_params).  What one context does per bar with a chain of launches per
+ * time step (tv_step), one kernel does for every bar and n_steps time steps in
+ * ONE launch: a lane per bar, the tridiagonal CG1 Newton systems solved
+ * directly (csrc/tv_ensemble.hip).  CG1 temperature and stress, reference
+ * model mode, no Dirichlet condition; anything else is refused (TV_ERR_ARG).
+ * Arguments are validated before the GPU is touched; without one, creation
+ * returns TV_ERR_HIP.  tv_last_error takes an ensemble handle too. */
+typedef struct {
+  int n_bars, n_cells;            /* >= 1 each */
+  const double* coords;           /* [n_bars][n_cells+1], strictly increasing per bar;
+                                     coords_shared != 0: one row used by every bar */
+  int coords_shared;
+  const double *htc, *T_0, *T_ambient, *epsilon, *alpha, *f;  /* n_bars each, or NULL = tv_params' value */
+} tv_ensemble_desc;
+
+int tv_ensemble_create(const tv_ensemble_desc* desc, const tv_fe_config* fe, const tv_params* shared,
+                       const tv_options* opts, int device, void** ens_out);
+int tv_ensemble_destroy(void* ens);
+/* T = T_prev = Tf = Tf_partial = each bar's own T_0 (as tv_set_initial_condition;
+ * the other fields and the Newton / failure records keep their values) */
+int tv_ensemble_set_initial_condition(void* ens);
+/* n_steps time steps of every bar (several launches when n_steps x nodes is
+ * large); returns when they have finished.  A bar whose Newton solve reaches
+ * newton_max_it unconverged does not end that step (tv_step's contract: T
+ * back to T_prev, the viscoelastic state that of the previous step) and is
+ * frozen for every later step and call; the other bars continue.  If a bar
+ * failed during this call and error_on_nonconvergence is set, the call
+ * returns TV_ERR_NOT_CONVERGED (tv_last_error names the first failed bar and
+ * its step); with the flag clear TV_OK.  tv_ensemble_stats tells either way. */
+int tv_ensemble_step(void* ens, int n_steps, int thermal_only);
+/* host <-> device, [bar][dof*bs + comp] (per bar the reference's interleaved
+ * layout); fields: TV_F_T, T_PREV, TF, TF_PARTIAL, PHI, XI, SIGMA, S_TILDE,
+ * SIGMA_TILDE -- every other id returns TV_ERR_STATE */
+int tv_ensemble_get_field(void* ens, int field, double* host, size_t n_values);
+int tv_ensemble_set_field(void* ens, int field, const double* host, size_t n_values);
+/* per bar (n_bars values each, any pointer may be NULL): Newton iterations of
+ * the bar's last solve, the 1-based step at which it failed (0 = none), and
+ * its Newton iterations summed over all steps */
+int tv_ensemble_stats(void* ens, int* newton_its_last, int* failed_step, int64_t* newton_total);
 
 /* ---- time-series output -------------------------------------------------------
  * The reference writes T, phi, Tf, xi (VTX/BP4) and sigma (XDMF/HDF5) every

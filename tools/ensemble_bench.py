@@ -1,0 +1,142 @@
+#!/usr/bin/env python
+"""Throughput of ThermoViscoEnsemble against one bar after another.
+
+Workload: the graded geometry.create_mesh bar, CG1 / CG1, the main.py
+parameters with htc spread linearly over 50 .. 1000, 500 steps (main.py's
+run).  Timed, each after a warm-up of the same shape:
+
+  * ensembles of 64, 1024, 4096 and 16384 bars: host clock around solve(),
+    which returns after the device has finished (median of --reps fresh
+    ensembles);
+  * the same work without the ensemble: 4 bars one after another through
+    ThermoViscoProblem, 500 steps each, the clock around solve() and a field
+    read that waits for the device (context creation left out); scaled
+    linearly to any ensemble size.
+
+Writes one JSON (default profiles/ensemble_bench.json): bar-steps/s per size,
+the sequential rate, the ratio, and the whole-solve fraction of the HBM peak
+from the kernel's algorithmic bytes ("1D ensembles"):
+
+  per node and Newton iteration   80 B  forward sweep reads T, T_prev and two
+                                        cell coefficients, writes the two
+                                        Thomas scratch values; back
+                                        substitution reads them and T, writes T
+  per node and step              344 B  the viscoelastic update: reads T,
+                                        T_prev, 6 Tf_partial, 12 tilde values;
+                                        writes 6 Tf_partial, Tf, phi, xi,
+                                        12 tilde values, sigma, T_prev
+
+The floor the design must hold: at 4096 bars at least 64x (one wavefront's
+width) the sequential bar-steps/s; the tool exits non-zero below it.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "fem-glass-tempering_amd")
+for p in (PKG, ROOT):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+HBM_PEAK = 8.0e12  # B/s, MI355X
+BYTES_NODE_NEWTON = 80
+BYTES_NODE_STEP = 344
+FLOOR = 64.0
+CFG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[64, 1024, 4096, 16384])
+    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--seq-bars", type=int, default=4)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ensemble_bench.json"))
+    args = ap.parse_args()
+
+    from geometry import graded_bar
+    from main import model_params
+    from tvfem import ThermoViscoEnsemble
+    from tvfem.problem import ThermoViscoProblem
+
+    mesh = graded_bar()
+    n_nodes = mesh.num_vertices
+    span = (0.0, args.steps * 0.1)
+
+    def ensemble(n_bars):
+        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFG, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)))
+        ens.setup()
+        return ens
+
+    rows = []
+    for n_bars in args.sizes:
+        warm = ensemble(n_bars)
+        warm.solve(5)
+        warm.close()
+        walls, its = [], 0.0
+        for _ in range(args.reps):
+            ens = ensemble(n_bars)
+            t0 = time.perf_counter()
+            ens.solve(args.steps)  # returns after the device has finished
+            walls.append(time.perf_counter() - t0)
+            assert not ens.failed_step.any()
+            its = float(ens.newton_total.mean()) / args.steps
+            ens.close()
+        wall = statistics.median(walls)
+        bar_steps = n_bars * args.steps
+        nbytes = bar_steps * n_nodes * (BYTES_NODE_NEWTON * its + BYTES_NODE_STEP)
+        rows.append({"n_bars": n_bars, "wall_s": wall, "wall_s_min": min(walls), "wall_s_max": max(walls),
+                     "bar_steps_per_s": bar_steps / wall, "newton_its_per_step": its,
+                     "algorithmic_bytes": nbytes, "hbm_fraction_of_8TBps": nbytes / wall / HBM_PEAK})
+        print(f"ensemble {n_bars:6d} bars: {wall * 1e3:9.2f} ms  {bar_steps / wall:12.4g} bar-steps/s  "
+              f"{its:.2f} Newton its/step  {nbytes / wall / HBM_PEAK:.2%} of HBM peak", flush=True)
+
+    # the same work one bar after another (what a parameter study costs without the ensemble)
+    def single(htc, steps):
+        prob = ThermoViscoProblem(mesh, span, 0.1, CFG, dict(model_params, htc=float(htc)), verbose=False,
+                                  write_output=False)
+        prob.setup()
+        t0 = time.perf_counter()
+        prob.solve(steps)
+        prob.get_field("T")  # waits for the queued work
+        wall = time.perf_counter() - t0
+        prob.close()
+        return wall
+
+    single(280.1, 5)
+    t0 = time.perf_counter()
+    seq_wall = sum(single(htc, args.steps) for htc in np.linspace(50.0, 1000.0, args.seq_bars))
+    seq_total = time.perf_counter() - t0
+    seq_rate = args.seq_bars * args.steps / seq_wall  # the time loops alone: context creation left out
+    print(f"sequential {args.seq_bars} bars: {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
+    for r in rows:
+        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
+    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "steps": args.steps, "dt": 0.1,
+                        "htc": "linspace(50, 1000, n_bars)", "families": "CG1/CG1", "reps": args.reps},
+           "bytes_model": {"per_node_newton_iteration": BYTES_NODE_NEWTON, "per_node_step": BYTES_NODE_STEP},
+           "ensemble": rows,
+           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
+                          "wall_s_with_context_creation": seq_total,
+                          "timed": "solve() and a final field read per bar; context creation and setup left out"},
+           "floor_ratio_at_4096": FLOOR}
+    at = [r for r in rows if r["n_bars"] == 4096]
+    if at:
+        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
+        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps({"out": args.out, "ratio_at_4096": res.get("ratio_at_4096")}))
+    if at and res["ratio_at_4096"] < FLOOR:
+        sys.exit(f"ensemble below the {FLOOR:g}x floor at 4096 bars")
+
+
+if __name__ == "__main__":
+    main()
