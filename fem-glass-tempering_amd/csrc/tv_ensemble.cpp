@@ -29,7 +29,13 @@ struct Ens {
   ViscoConst vc{};
   ViscoFields vf{};
   std::vector<double> T0;     // per bar
-  std::vector<void*> bufs;    // every device allocation
+  std::vector<double> par;    // [3][n_bars] htc, T_ambient, epsilon as created (a schedule's NULL tables)
+  std::vector<void*> bufs;    // every device allocation that lives as long as the handle
+  EnsExt x{};                 // schedule and history as the kernel reads them ...
+  EnsExt* dx = nullptr;       // ... and their device copy (in bufs)
+  void* sched_buf = nullptr;  // the stage tables in one allocation
+  void* hist_buf = nullptr;   // the records, then the probe nodes
+  bool ext() const { return x.n_stages > 0 || x.n_probes > 0; }
   double* field[TV_NUM_FIELDS] = {};
   int bs[TV_NUM_FIELDS] = {};
   int steps_done = 0;
@@ -88,6 +94,19 @@ int ens_transfer(Ens* c, int field, double* host, size_t n_values, bool to_devic
     HIPC(hipMemcpyAsync(c->field[field], dev.data(), bytes, hipMemcpyHostToDevice, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
   }
+  return TV_OK;
+}
+
+// the kernel reads schedule and history through the device copy of Ens::x (allocated with the first
+// of either, so an ensemble without them allocates what it always did)
+int ens_push_ext(Ens* c) {
+  if (!c->dx) {
+    void* p = nullptr;
+    if (int e = ens_alloc(c, sizeof(EnsExt), &p)) return e;
+    c->dx = static_cast<EnsExt*>(p);
+  }
+  HIPC(hipMemcpyAsync(c->dx, &c->x, sizeof(EnsExt), hipMemcpyHostToDevice, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
   return TV_OK;
 }
 
@@ -206,6 +225,9 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   a.its_last = static_cast<int*>(its);
   a.failed_step = static_cast<int*>(fs);
   a.newton_total = static_cast<int64_t*>(tot);
+  c->x.every = 1;
+  c->par.resize((size_t)3 * nb);
+  for (int q = 0; q < 3; ++q) std::copy_n(par.begin() + (size_t)q * pad, nb, c->par.begin() + (size_t)q * nb);
   // the shared viscoelastic constants, as visco_setup (tv_solver.cpp) forms them
   ViscoConst& k = c->vc;
   k.H_over_Rg = P->H / P->Rg;
@@ -249,6 +271,8 @@ int tv_ensemble_destroy(void* ens) {
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
   for (void* p : c->bufs) hipFree(p);
+  hipFree(c->sched_buf);
+  hipFree(c->hist_buf);
   hipStreamDestroy(c->stream);
   delete c;
   return TV_OK;
@@ -280,6 +304,10 @@ int tv_ensemble_step(void* ens, int n_steps, int thermal_only) {
   if (!c) return TV_ERR_ARG;
   if (n_steps < 0 || (int64_t)c->steps_done + n_steps > INT32_MAX - 1)
     return c->fail(TV_ERR_ARG, "tv_ensemble_step: n_steps out of range");
+  if (c->x.n_probes > 0 && (int64_t)c->steps_done + n_steps > (int64_t)c->x.max_records * c->x.every)
+    return c->fail(TV_ERR_STATE, "tv_ensemble_step: step " + std::to_string((int64_t)c->steps_done + n_steps) +
+                                     " lies past the open history (max_records " + std::to_string(c->x.max_records) +
+                                     " x every " + std::to_string(c->x.every) + "); no bar has advanced");
   hipSetDevice(c->device);
   const int before = c->steps_done;
   const int per_launch = (int)std::max<int64_t>(1, kMaxNodeStepsPerLaunch / c->a.n_nodes);
@@ -288,7 +316,7 @@ int tv_ensemble_step(void* ens, int n_steps, int thermal_only) {
     a.n_steps = std::min(left, per_launch);
     a.step_base = c->steps_done;
     a.thermal_only = thermal_only ? 1 : 0;
-    launch_ensemble(a, c->vc, c->vf, c->stream);
+    launch_ensemble(a, c->vc, c->vf, c->ext() ? c->dx : nullptr, c->stream);
     HIPC(hipGetLastError());
     c->steps_done += a.n_steps;
     left -= a.n_steps;
@@ -335,6 +363,165 @@ int tv_ensemble_stats(void* ens, int* newton_its_last, int* failed_step, int64_t
   if (newton_total)
     HIPC(hipMemcpyAsync(newton_total, c->a.newton_total, sizeof(int64_t) * nb, hipMemcpyDeviceToHost, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
+  return TV_OK;
+}
+
+
+int tv_ensemble_set_schedule(void* ens, const tv_ensemble_schedule* s) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  if (!s) {  // back to the creation values
+    hipFree(c->sched_buf);  // no launch is in flight: tv_ensemble_step returns after its launches
+    c->sched_buf = nullptr;
+    c->x.n_stages = 0;
+    c->x.stage_end = nullptr;
+    c->x.htc = c->x.T_amb = c->x.eps = nullptr;
+    return ens_push_ext(c);
+  }
+  auto bad = [&](const std::string& m) { return c->fail(TV_ERR_ARG, "tv_ensemble_set_schedule: " + m); };
+  const int nst = s->n_stages, nb = c->a.n_bars;
+  const int64_t pad = c->a.nb_pad;
+  if (nst < 1) return bad("n_stages must be at least 1");
+  if ((nst == 1) != (s->stage_end == nullptr))
+    return bad("stage_end is NULL if and only if n_stages == 1");
+  if (nst * pad > INT32_MAX) return bad("schedule too large");
+  for (int b = 0; b < nb; ++b)
+    for (int j = 0, prev = 0; j + 1 < nst; ++j) {
+      const int e = s->stage_end[(size_t)j * nb + b];
+      if (e < 0) return bad("stage_end of bar " + std::to_string(b) + ", stage " + std::to_string(j) + " is negative");
+      if (e < prev)
+        return bad("stage_end of bar " + std::to_string(b) + " decreases at stage " + std::to_string(j));
+      prev = e;
+    }
+  const double* tab[3] = {s->htc, s->T_ambient, s->epsilon};
+  static const char* const kName[3] = {"htc", "T_ambient", "epsilon"};
+  for (int q = 0; q < 3; ++q)
+    for (size_t i = 0; tab[q] && i < (size_t)nst * nb; ++i)
+      if (!std::isfinite(tab[q][i]))
+        return bad(std::string(kName[q]) + " of bar " + std::to_string(i % nb) + ", stage " + std::to_string(i / nb) +
+                   " is not finite");
+  // device rows (EnsExt): per bar its non-empty stages in order, the last stage closing the list
+  // with INT32_MAX and repeated down to row nst - 1; padding lanes (never read) hold the same end
+  const size_t rows = (size_t)nst * pad;
+  std::vector<double> val(3 * rows, 0.0);
+  std::vector<int> end(rows, INT32_MAX);
+  for (int b = 0; b < nb; ++b) {
+    int row = 0, prev = 0;
+    auto put = [&](int j, int e) {
+      for (int q = 0; q < 3; ++q)
+        val[q * rows + (size_t)row * pad + b] = tab[q] ? tab[q][(size_t)j * nb + b] : c->par[(size_t)q * nb + b];
+      end[(size_t)row * pad + b] = e;
+    };
+    int last = nst - 1;  // the stage that never ends: the last one, or one whose end no step can pass
+    for (int j = 0; j + 1 < nst; ++j) {
+      const int e = s->stage_end[(size_t)j * nb + b];
+      if (e == prev) continue;  // empty
+      if (e == INT32_MAX) {
+        last = j;
+        break;
+      }
+      put(j, e);
+      prev = e;
+      ++row;
+    }
+    for (; row < nst; ++row) put(last, INT32_MAX);
+  }
+  void* buf = nullptr;
+  HIPC(hipMalloc(&buf, val.size() * sizeof(double) + end.size() * sizeof(int)));
+  double* dval = static_cast<double*>(buf);
+  int* dend = reinterpret_cast<int*>(dval + val.size());
+  hipError_t e1 = hipMemcpyAsync(dval, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
+  hipError_t e2 = hipMemcpyAsync(dend, end.data(), end.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
+  hipError_t e3 = hipStreamSynchronize(c->stream);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+    hipFree(buf);
+    return c->fail(TV_ERR_HIP, "tv_ensemble_set_schedule: upload failed");
+  }
+  hipFree(c->sched_buf);
+  c->sched_buf = buf;
+  c->x.n_stages = nst;
+  c->x.stage_end = dend;
+  c->x.htc = dval;
+  c->x.T_amb = dval + rows;
+  c->x.eps = dval + 2 * rows;
+  return ens_push_ext(c);
+}
+
+
+int tv_ensemble_history_open(void* ens, int n_probes, const int* dofs, int every, int max_records) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  auto bad = [&](const std::string& m) { return c->fail(TV_ERR_ARG, "tv_ensemble_history_open: " + m); };
+  if (n_probes < 0) return bad("n_probes is negative");
+  if (n_probes == 0) {  // close: the records go, the step cap with them
+    hipFree(c->hist_buf);
+    c->hist_buf = nullptr;
+    c->x.n_probes = 0;
+    c->x.every = 1;
+    c->x.max_records = 0;
+    c->x.probes = nullptr;
+    c->x.hist = nullptr;
+    return ens_push_ext(c);
+  }
+  if (!dofs) return bad("dofs is null");
+  if (every < 1) return bad("every must be at least 1");
+  if (max_records < 1) return bad("max_records must be at least 1");
+  for (int p = 0; p < n_probes; ++p)
+    if (dofs[p] < 0 || dofs[p] >= c->a.n_nodes)
+      return bad("probe " + std::to_string(p) + " (dof " + std::to_string(dofs[p]) + ") lies outside [0, n_cells = " +
+                 std::to_string(c->a.n_nodes - 1) + "]");
+  const int64_t pad = c->a.nb_pad;
+  if ((int64_t)max_records * every > INT32_MAX - 1) return bad("max_records x every exceeds the step range");
+  if ((double)max_records * 3.0 * n_probes * (double)pad > (double)(INT64_C(1) << 37)) return bad("history too large");
+  const size_t n_val = (size_t)max_records * 3 * n_probes * pad;
+  void* buf = nullptr;
+  HIPC(hipMalloc(&buf, n_val * sizeof(double) + (size_t)n_probes * sizeof(int)));
+  double* dh = static_cast<double*>(buf);
+  int* dprobes = reinterpret_cast<int*>(dh + n_val);
+  // all bits set is a NaN: what a record reads until its step has written it
+  hipError_t e1 = hipMemsetAsync(dh, 0xFF, n_val * sizeof(double), c->stream);
+  hipError_t e2 = hipMemcpyAsync(dprobes, dofs, (size_t)n_probes * sizeof(int), hipMemcpyHostToDevice, c->stream);
+  hipError_t e3 = hipStreamSynchronize(c->stream);
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
+    hipFree(buf);
+    return c->fail(TV_ERR_HIP, "tv_ensemble_history_open: device setup failed");
+  }
+  hipFree(c->hist_buf);
+  c->hist_buf = buf;
+  c->x.n_probes = n_probes;
+  c->x.every = every;
+  c->x.max_records = max_records;
+  c->x.probes = dprobes;
+  c->x.hist = dh;
+  return ens_push_ext(c);
+}
+
+
+int tv_ensemble_history_read(void* ens, double* host, size_t n_values, int* n_records) {
+  Ens* c = static_cast<Ens*>(ens);
+  if (!c) return TV_ERR_ARG;
+  hipSetDevice(c->device);
+  if (c->x.n_probes == 0) return c->fail(TV_ERR_STATE, "tv_ensemble_history_read: no history is open");
+  const int nrec = std::min(c->steps_done / c->x.every, c->x.max_records);
+  if (n_records) *n_records = nrec;
+  if (!host) {
+    if (n_records) return TV_OK;  // a query of the record count
+    return c->fail(TV_ERR_ARG, "tv_ensemble_history_read: host and n_records are both null");
+  }
+  const int np = c->x.n_probes, nb = c->a.n_bars;
+  const int64_t pad = c->a.nb_pad;
+  if (n_values < (size_t)nrec * 3 * nb * np)
+    return c->fail(TV_ERR_ARG, "tv_ensemble_history_read: host holds fewer than n_records x 3 x n_bars x n_probes values");
+  if (nrec == 0) return TV_OK;
+  // device [record][field][probe][bar_pad]  ->  host [record][field][bar][probe]
+  std::vector<double> dev((size_t)nrec * 3 * np * pad);
+  HIPC(hipMemcpyAsync(dev.data(), c->x.hist, dev.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  for (size_t rf = 0; rf < (size_t)nrec * 3; ++rf)
+    for (int b = 0; b < nb; ++b)
+      for (int p = 0; p < np; ++p) host[(rf * nb + b) * np + p] = dev[(rf * np + p) * pad + b];
   return TV_OK;
 }
 

@@ -28,6 +28,14 @@
 // converge at different Newton counts; a converged lane idles until the
 // slowest bar of its wave is done.
 //
+// Process schedules and probe histories (EnsExt, the kExt instantiation): a
+// bar's htc / T_ambient / epsilon may change at per-bar step numbers, the
+// values of step s being those of the stage that holds s (the new time level,
+// as every other implicit Euler term); and after every `every`-th step the
+// lane stores T, Tf and sigma at a few shared probe nodes into
+// [record][field][probe][bar], one contiguous segment per store of a wave.  A
+// failed bar stores nothing more.  Without either the plain instantiation runs.
+//
 // The Thomas recurrences are one dependent divide chain per bar, but no
 // address depends on them: both sweeps walk the nodes in chunks of kChunk and
 // issue the loads of the next chunk before the chain of the current one.
@@ -144,7 +152,24 @@ __device__ __forceinline__ double newton_iteration(const EnsArgs& a, const Bar& 
   return nrm2;
 }
 
-__global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, ViscoFields f) {
+// The bar's Robin coefficients from its (current stage's) htc, T_ambient, epsilon
+__device__ __forceinline__ void set_boundary(Bar& b, double sigma_sb, double htc, double Ta, double eps) {
+  const double Ta2 = Ta * Ta;
+  b.a_rad = 0.001 * (sigma_sb * eps);
+  b.a_conv = 0.001 * htc;
+  b.T_amb = Ta;
+  b.T_amb4 = Ta2 * Ta2;
+}
+
+// kExt = false: constant boundary values, final state only; x is not read and
+// the instructions are those of the kernel before schedules existed.
+// kExt = true: per-bar stage tables and / or probe records (EnsExt).  A lane
+// keeps its own stage and that stage's last step; both follow from the
+// absolute step alone, so a launch may start at any step.  Lanes of a wave
+// may sit in different stages: that predicates the reload of three values,
+// no address pattern changes.
+template <bool kExt>
+__global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, ViscoFields f, const EnsExt* __restrict__ x) {
   const int64_t bar = blockIdx.x * (int64_t)kWave + threadIdx.x;
   if (bar >= a.n_bars) return;        // tail lanes: no memory access
   if (a.failed_step[bar] != 0) return;  // frozen by an earlier failure
@@ -160,9 +185,32 @@ __global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, Vis
     b.dt = a.dt;
     b.dtf = a.dt * a.f[bar];
   }
+  // kExt: the bar's stage and that stage's last step.  The host has dropped the
+  // empty stages of each bar and closed its list with INT32_MAX, so the ends
+  // rise strictly and passing one means exactly the next row.
+  int stage = 0, stage_last = INT32_MAX;
+  if constexpr (kExt) {
+    if (x->n_stages > 0) {
+      stage_last = x->stage_end[bar];
+      while (a.step_base + 1 > stage_last) {  // ends at the latest in the bar's last row (INT32_MAX)
+        ++stage;
+        stage_last = x->stage_end[(int64_t)stage * a.nb_pad + bar];
+      }
+      const int64_t t = (int64_t)stage * a.nb_pad + bar;
+      set_boundary(b, a.sigma_sb, x->htc[t], x->T_amb[t], x->eps[t]);
+    }
+  }
   int its = 0, failed = 0;
   int64_t total = 0;
   for (int s = 0; s < a.n_steps; ++s) {
+    if constexpr (kExt) {
+      if (a.step_base + s + 1 > stage_last) {
+        ++stage;
+        const int64_t t = (int64_t)stage * a.nb_pad + bar;
+        stage_last = x->stage_end[t];
+        set_boundary(b, a.sigma_sb, x->htc[t], x->T_amb[t], x->eps[t]);
+      }
+    }
     its = 0;
     bool conv = false;
     double r0 = 0.0;
@@ -193,6 +241,20 @@ __global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, Vis
         f.Tp[t] = ts.T;
       }
     }
+    if constexpr (kExt) {
+      // record step / every - 1 of [record][field][probe][bar]: T, Tf, sigma as this step left them
+      // (the host refuses steps past max_records * every; the bound here only keeps the stores inside)
+      const int step = a.step_base + s + 1;
+      if (x->n_probes > 0 && step % x->every == 0 && step / x->every <= x->max_records) {
+        const int64_t rec = (int64_t)(step / x->every - 1) * 3 * x->n_probes;
+        for (int p = 0; p < x->n_probes; ++p) {
+          const int64_t t = (int64_t)x->probes[p] * a.nb_pad + bar;
+          x->hist[(rec + p) * a.nb_pad + bar] = a.T[t];
+          x->hist[(rec + x->n_probes + p) * a.nb_pad + bar] = f.Tf[t];
+          x->hist[(rec + 2 * x->n_probes + p) * a.nb_pad + bar] = f.sigma[t];
+        }
+      }
+    }
   }
   a.its_last[bar] = its;
   a.newton_total[bar] += total;
@@ -201,8 +263,9 @@ __global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, Vis
 
 }  // namespace
 
-void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, hipStream_t s) {
-  hipLaunchKernelGGL(k_ensemble, dim3(a.nb_pad / kWave), dim3(kWave), 0, s, a, c, f);
+void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s) {
+  if (x) hipLaunchKernelGGL(k_ensemble<true>, dim3(a.nb_pad / kWave), dim3(kWave), 0, s, a, c, f, x);
+  else hipLaunchKernelGGL(k_ensemble<false>, dim3(a.nb_pad / kWave), dim3(kWave), 0, s, a, c, f, nullptr);
 }
 
 }  // namespace tv

@@ -420,7 +420,26 @@ struct EnsArgs {
   int* failed_step;           // [nb_pad] 0, or the step at which the bar failed (frozen from then on)
   int64_t* newton_total;      // [nb_pad]
 };
-void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, hipStream_t s);
+// Process schedule and probe records of an ensemble: read by the second
+// instantiation of the kernel only, through a device pointer, so that its
+// fields are fetched where a stage changes or a record is due and do not sit
+// in registers through the sweeps.  The stage rows are per bar those of its
+// non-empty stages in order, the last one repeated down to row n_stages - 1;
+// stage_end of a bar's last stage is INT32_MAX, so the ends rise strictly
+// and the kernel moves exactly one row when a step passes one.
+struct EnsExt {
+  int n_stages;               // 0: no schedule, the bars keep EnsArgs' htc / T_amb / eps
+  int n_probes;               // 0: no history
+  int every, max_records;     // a record after every `every`-th absolute step, at most max_records
+  const int* stage_end;       // [n_stages][nb_pad] last absolute step (1-based) of the row's stage
+  const double* htc;          // [n_stages][nb_pad] each
+  const double* T_amb;
+  const double* eps;
+  const int* probes;          // [n_probes] node of each probe, the same for every bar
+  double* hist;               // [max_records][3 (T, Tf, sigma)][n_probes][nb_pad]
+};
+// x: device pointer, or nullptr for the plain kernel
+void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);
 
 // PCG vector kernels over the owned range [0, n) of already-offset pointers
 constexpr int kVecBlocks = 1024;        // grid cap of the vector kernels

@@ -43,6 +43,7 @@ EXPORTS = [
     "tv_xdmf_add_field", "tv_xdmf_append", "tv_xdmf_close",
     "tv_ensemble_create", "tv_ensemble_destroy", "tv_ensemble_set_initial_condition", "tv_ensemble_step",
     "tv_ensemble_get_field", "tv_ensemble_set_field", "tv_ensemble_stats",
+    "tv_ensemble_set_schedule", "tv_ensemble_history_open", "tv_ensemble_history_read",
 ]
 
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
@@ -77,6 +78,11 @@ class EnsembleDesc(C.Structure):
     _fields_ = ([("n_bars", C.c_int), ("n_cells", C.c_int), ("coords", C.POINTER(C.c_double)),
                  ("coords_shared", C.c_int)]
                 + [(n, C.POINTER(C.c_double)) for n in ("htc", "T_0", "T_ambient", "epsilon", "alpha", "f")])
+
+
+class EnsembleSchedule(C.Structure):
+    _fields_ = ([("n_stages", C.c_int), ("stage_end", C.POINTER(C.c_int))]
+                + [(n, C.POINTER(C.c_double)) for n in ("htc", "T_ambient", "epsilon")])
 
 
 class FeConfig(C.Structure):
@@ -191,6 +197,9 @@ def load_library():
         "tv_ensemble_get_field": (C.c_int, [vp, C.c_int, dp, C.c_size_t]),
         "tv_ensemble_set_field": (C.c_int, [vp, C.c_int, dp, C.c_size_t]),
         "tv_ensemble_stats": (C.c_int, [vp, ip, ip, i64p]),
+        "tv_ensemble_set_schedule": (C.c_int, [vp, C.POINTER(EnsembleSchedule)]),
+        "tv_ensemble_history_open": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int]),
+        "tv_ensemble_history_read": (C.c_int, [vp, dp, C.c_size_t, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

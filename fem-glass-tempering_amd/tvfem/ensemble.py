@@ -12,6 +12,23 @@ parameter are shared.  CG1 temperature and stress, reference model mode.
     ens.setup()
     ens.solve()
     sigma = ens.get_field("sigma")        # (n_bars, n_dofs)
+
+A process schedule lets ``htc``, ``T_ambient`` and ``epsilon`` of each bar change
+at times of its own (a quench of per-bar length, then after-cooling), and a
+probe history has the kernel record T, Tf and sigma at a few nodes while it
+runs, so that a transient is read without cutting the run into calls:
+
+    ens = ThermoViscoEnsemble(mesh, (0.0, 50.0), 0.1, fe_config, model_params,
+            schedule=[dict(until=np.linspace(2.0, 10.0, 4096).round(1), htc=900.0, T_ambient=293.0),
+                      dict(htc=60.0)],                      # last stage: no end
+            history=dict(nodes=[0, 24, 48], every=5))
+    ens.setup(); ens.solve()
+    h = ens.get_history()   # {"step": (R,), "t": (R,), "T" / "Tf" / "sigma": (R, n_bars, n_probes)}
+
+Every stage but the last carries exactly one of ``until`` (a time, on the step
+grid) or ``until_step``; step s (1-based) belongs to the first stage whose end
+is not before it, so equal ends give an empty stage.  The other keys are scalars
+or per-bar arrays; a missing key keeps the bar's ``model_parameters`` value.
 """
 from __future__ import annotations
 
@@ -29,13 +46,41 @@ PER_BAR_KEYS = ("htc", "T_0", "T_ambient", "epsilon", "alpha", "f")
 STATE_FIELDS = {"T": 1, "T_prev": 1, "Tf": 1, "Tf_partial": 6, "phi": 1, "xi": 1, "sigma": 1,
                 "s_tilde_partial": 6, "sigma_tilde_partial": 6}
 _FAMILIES = {"CG": N.TV_CG, "DG": N.TV_DG}
+# what a schedule stage may change, and how it says where it ends
+STAGE_KEYS = ("htc", "T_ambient", "epsilon")
+STAGE_ENDS = ("until", "until_step")
+
+
+def _parse_stages(schedule):
+    """The stages as dicts of scalars / 1D arrays, their keys checked (the sizes
+    and the step grid are checked once n_bars and the time span are known)."""
+    stages = [dict(st) for st in schedule]
+    if not stages:
+        raise ValueError("schedule: at least one stage")
+    for j, st in enumerate(stages):
+        unknown = set(st) - set(STAGE_KEYS) - set(STAGE_ENDS)
+        if unknown:
+            raise ValueError(f"schedule stage {j}: unknown key(s) {sorted(unknown)} "
+                             f"({', '.join(STAGE_ENDS + STAGE_KEYS)})")
+        n_ends = sum(k in st for k in STAGE_ENDS)
+        if j == len(stages) - 1 and n_ends:
+            raise ValueError("schedule: the last stage never ends (no until / until_step)")
+        if j < len(stages) - 1 and n_ends != 1:
+            raise ValueError(f"schedule stage {j}: exactly one of until / until_step (only the last stage has none)")
+        for key, val in st.items():
+            if np.ndim(val) > 1:
+                raise ValueError(f"schedule stage {j}: {key} is a scalar or one value per bar")
+            if np.ndim(val) == 1:
+                st[key] = np.asarray(val, dtype=np.float64)
+    return stages
 
 
 class ThermoViscoEnsemble:
     def __init__(self, meshes, time: tuple, dt: float, config: dict, model_parameters: dict, *,
                  n_bars: int | None = None, device: int = 0, model_mode: str = "reference",
                  newton_rtol: float | None = None, newton_atol: float | None = None,
-                 newton_max_it: int | None = None, error_on_nonconvergence: bool = True) -> None:
+                 newton_max_it: int | None = None, error_on_nonconvergence: bool = True,
+                 schedule=None, history: dict | None = None) -> None:
         self._ens = None
         # ---- meshes: one 1D RectilinearMesh for all bars, or one per bar
         shared = isinstance(meshes, RectilinearMesh)
@@ -56,7 +101,10 @@ class ThermoViscoEnsemble:
                 raise ValueError(f"model parameter {key!r} is shared by the ensemble and must be a scalar "
                                  f"(per-bar arrays: {', '.join(PER_BAR_KEYS)})")
             arrays[key] = np.ascontiguousarray(val, dtype=np.float64).reshape(-1)
+        stages = _parse_stages(schedule) if schedule is not None else None
         sizes = {len(v) for v in arrays.values()}
+        if stages is not None:
+            sizes |= {len(v) for st in stages for v in st.values() if np.ndim(v) == 1}
         if not shared:
             sizes.add(len(mlist))
         if n_bars is not None:
@@ -76,6 +124,9 @@ class ThermoViscoEnsemble:
         self.config = config
         self.coords = np.ascontiguousarray(np.stack([m.axes[0] for m in mlist]))
         self._arrays = arrays
+        # ---- process schedule and probe history: everything is decided before anything is created
+        self._schedule = None if stages is None else self._stage_tables(stages, mp)
+        self._history = None if history is None else self._history_args(history)
         # ---- native handle
         lib = N.load_library()
         self._lib = lib
@@ -103,6 +154,80 @@ class ThermoViscoEnsemble:
         N.check(lib.tv_ensemble_create(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), device,
                                        C.byref(ens)))
         self._ens = ens
+        try:
+            if self._schedule is not None:
+                end, tabs = self._schedule
+                sch = N.EnsembleSchedule()
+                sch.n_stages = len(stages)
+                if end is not None:
+                    sch.stage_end = end.ctypes.data_as(C.POINTER(C.c_int))
+                for key, tab in tabs.items():
+                    setattr(sch, key, tab.ctypes.data_as(C.POINTER(C.c_double)))
+                N.check(lib.tv_ensemble_set_schedule(ens, C.byref(sch)), ens)
+            if self._history is not None:
+                nodes, every, max_records = self._history
+                N.check(lib.tv_ensemble_history_open(ens, len(nodes), nodes.ctypes.data_as(C.POINTER(C.c_int)),
+                                                     every, max_records), ens)
+        except Exception:
+            self.close()
+            raise
+
+    def _stage_tables(self, stages, mp):
+        """(stage_end [n_stages-1][n_bars] or None, {key: [n_stages][n_bars]}) of the parsed stages."""
+        nb, nst = self.n_bars, len(stages)
+        end = np.zeros((nst - 1, nb), dtype=np.intc) if nst > 1 else None
+        for j, st in enumerate(stages[:-1]):
+            if "until_step" in st:
+                k = np.broadcast_to(np.asarray(st["until_step"]), (nb,))
+                if not np.all(np.isfinite(k)) or np.any(k != np.round(k)):
+                    raise ValueError(f"schedule stage {j}: until_step must be whole steps")
+            else:
+                x = (np.broadcast_to(np.asarray(st["until"], dtype=np.float64), (nb,)) - self.time[0]) / self.dt
+                k = np.round(x)
+                off = ~(np.abs(x - k) <= 1e-6)  # also catches NaN
+                if off.any():
+                    b = int(np.argmax(off))
+                    raise ValueError(f"schedule stage {j}: until of bar {b} is not on the step grid "
+                                     f"(time[0] + k dt within 1e-6 dt)")
+            if np.any(k < 0) or np.any(k > np.iinfo(np.intc).max):
+                raise ValueError(f"schedule stage {j}: the stage ends before the start (or out of range) "
+                                 f"for bar {int(np.argmax((k < 0) | (k > np.iinfo(np.intc).max)))}")
+            end[j] = k
+            if j and np.any(end[j] < end[j - 1]):
+                b = int(np.argmax(end[j] < end[j - 1]))
+                raise ValueError(f"schedule: the stage ends of bar {b} decrease at stage {j} "
+                                 f"({int(end[j - 1][b])} then {int(end[j][b])})")
+        tabs = {}
+        for key in STAGE_KEYS:
+            if not any(key in st for st in stages):
+                continue  # NULL table: the creation value in every stage
+            own = self._arrays.get(key, mp[key])  # a missing key takes the bar's model_parameters value
+            tab = np.empty((nst, nb))
+            for j, st in enumerate(stages):
+                tab[j] = st.get(key, own)
+            if not np.all(np.isfinite(tab)):
+                raise ValueError(f"schedule: {key} is not finite")
+            tabs[key] = tab
+        return end, tabs
+
+    def _history_args(self, history):
+        unknown = set(history) - {"nodes", "every", "max_records"}
+        if unknown:
+            raise ValueError(f"history: unknown key(s) {sorted(unknown)} (nodes, every, max_records)")
+        if "nodes" not in history:
+            raise ValueError("history: nodes is required")
+        nodes = np.atleast_1d(np.asarray(history["nodes"]))
+        if nodes.ndim != 1 or nodes.size == 0 or np.any(nodes != np.round(nodes)):
+            raise ValueError("history: nodes is a non-empty list of dof numbers")
+        if np.any(nodes < 0) or np.any(nodes > self.n_cells):
+            raise ValueError(f"history: probe node outside [0, n_cells = {self.n_cells}]")
+        every = int(history.get("every", 1))
+        if every < 1:
+            raise ValueError("history: every must be at least 1")
+        max_records = int(history.get("max_records", max(self.n_steps // every, 1)))
+        if max_records < 1:
+            raise ValueError("history: max_records must be at least 1")
+        return np.ascontiguousarray(nodes, dtype=np.intc), every, max_records
 
     # ---- reference-style driver -----------------------------------------------------------
     def setup(self) -> None:
@@ -135,6 +260,22 @@ class ThermoViscoEnsemble:
         v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
         N.check(self._lib.tv_ensemble_set_field(self._ens, N.FIELD_ID[name],
                                                 v.ctypes.data_as(C.POINTER(C.c_double)), v.size), self._ens)
+
+    def get_history(self) -> dict:
+        """The probe records so far: ``step`` and ``t`` of shape (R,), ``T``, ``Tf`` and
+        ``sigma`` of shape (R, n_bars, n_probes); record r is the state after step
+        (r + 1) * every.  NaN where a bar had failed or the history was not yet open."""
+        if self._history is None:
+            raise ValueError("the ensemble was created without history=")
+        nodes, every, _ = self._history
+        n_rec = C.c_int(0)
+        N.check(self._lib.tv_ensemble_history_read(self._ens, None, 0, C.byref(n_rec)), self._ens)
+        out = np.empty((n_rec.value, 3, self.n_bars, len(nodes)))
+        N.check(self._lib.tv_ensemble_history_read(self._ens, out.ctypes.data_as(C.POINTER(C.c_double)), out.size,
+                                                   C.byref(n_rec)), self._ens)
+        step = (np.arange(n_rec.value) + 1) * every
+        return {"step": step, "t": self.time[0] + step * self.dt, "T": out[:, 0], "Tf": out[:, 1],
+                "sigma": out[:, 2]}
 
     def _stats(self):
         its = np.zeros(self.n_bars, dtype=np.intc)

@@ -59,7 +59,8 @@ extern "C" {
                             7: tv_get_options, tv_set_newton_tolerances, tv_set_ksp_tolerances,
                                tv_last_converged;
                             8: tv_options lost the unused use_graphs field;
-                               (still 8, additions only: tv_ensemble_desc and the tv_ensemble_* functions) */
+                               (still 8, additions only: tv_ensemble_desc and the tv_ensemble_* functions;
+                               then tv_ensemble_schedule, tv_ensemble_set_schedule, tv_ensemble_history_*) */
 
 /* status codes */
 #define TV_OK 0
@@ -433,6 +434,46 @@ int tv_ensemble_set_field(void* ens, int field, const double* host, size_t n_val
  * the bar's last solve, the 1-based step at which it failed (0 = none), and
  * its Newton iterations summed over all steps */
 int tv_ensemble_stats(void* ens, int* newton_its_last, int* failed_step, int64_t* newton_total);
+
+/* Process schedules: htc, T_ambient and epsilon of a bar change at step numbers
+ * of its own (a strong quench, then after-cooling).  n_stages >= 1 stages per
+ * bar; stage j of bar b covers the absolute steps end[j-1][b] < s <= end[j][b]
+ * (s 1-based, counted as failed_step counts; end[-1] = 0; the last stage never
+ * ends).  Ends are >= 0 and non-decreasing in j per bar; equal ends give an
+ * empty stage that is skipped, so one ensemble can hold bars with no, a short
+ * and a long quench.  During step s a bar uses its stage's three values in the
+ * residual and the Jacobian -- the values valid at the new time level, as the
+ * implicit Euler form takes every other term.  Tables are stage-major,
+ * [stage][bar]; a NULL table means the bar's creation value in every stage.
+ * Everything is validated before anything is uploaded (TV_ERR_ARG; the
+ * message names the first offending bar).  The schedule takes effect from the
+ * next step and depends on the absolute step only, so it does not matter how
+ * the steps are split over calls.  schedule == NULL clears it. */
+typedef struct {
+  int n_stages;                              /* >= 1 */
+  const int* stage_end;                      /* [n_stages-1][n_bars]; NULL iff n_stages == 1 */
+  const double *htc, *T_ambient, *epsilon;   /* [n_stages][n_bars] each, or NULL */
+} tv_ensemble_schedule;
+int tv_ensemble_set_schedule(void* ens, const tv_ensemble_schedule* schedule);
+
+/* Probe histories: record r holds T, Tf and sigma at n_probes dofs (shared by
+ * all bars, each in [0, n_cells], duplicates allowed) of every bar after the
+ * absolute step (r+1)*every, written by the kernel as it finishes that step --
+ * a transient (the surface tension peak of a quench) without cutting the run
+ * into calls.  The buffer holds max_records records and is NaN when opened:
+ * steps taken before the opening stay NaN, and so do the records of a failed
+ * bar from its failed step on (a frozen bar writes nothing).  While a history
+ * is open tv_ensemble_step returns TV_ERR_STATE, before it launches anything,
+ * if the call would pass step max_records*every.  Thermal-only steps record
+ * what the state holds.  n_probes == 0 frees the buffer and lifts the cap;
+ * opening again replaces the buffer. */
+int tv_ensemble_history_open(void* ens, int n_probes, const int* dofs, int every, int max_records);
+/* host[n_records][3 (T, Tf, sigma)][n_bars][n_probes], n_records =
+ * min(steps done / every, max_records), also stored to *n_records (may be
+ * NULL).  host holds n_values doubles, at least that many (TV_ERR_ARG
+ * otherwise); host == NULL only asks for n_records.  TV_ERR_STATE if no
+ * history is open. */
+int tv_ensemble_history_read(void* ens, double* host, size_t n_values, int* n_records);
 
 /* ---- time-series output -------------------------------------------------------
  * The reference writes T, phi, Tf, xi (VTX/BP4) and sigma (XDMF/HDF5) every

@@ -28,12 +28,24 @@ from the kernel's algorithmic bytes ("1D ensembles"):
 
 The floor the design must hold: at 4096 bars at least 64x (one wavefront's
 width) the sequential bar-steps/s; the tool exits non-zero below it.
+
+--scheduled measures what process schedules and probe histories cost instead
+(default output profiles/ensemble_schedule_bench.json): per size the wall time
+of the same run without a schedule, of a two-stage run (per-bar quench ends
+spread over steps 20 .. 100, htc 900 -> 60, three probes, a record every 10
+steps), and -- with --parent-tree, a built checkout of the parent commit --
+of the unscheduled run there, measured by the parent's own copy of this tool
+in a child process of the same session (numbers of different machines or days
+are not comparable).  The margin the two new figures are held against is
+the larger of 2 % and three times the parent's own rep-to-rep spread.
 """
 import argparse
 import json
 import os
 import statistics
+import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -49,6 +61,121 @@ BYTES_NODE_NEWTON = 80
 BYTES_NODE_STEP = 344
 FLOOR = 64.0
 CFG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
+# the cross-compiler's resource report of csrc/tv_ensemble.hip (gfx950, -O3 -ffp-contract=off), recorded with
+# the change that added schedules; DESIGN.md section 15 says how it was obtained
+KERNEL_RECORD = {
+    "plain_instantiation": {"vgpr_count": 234, "sgpr_spill_count": 63, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0,
+                            "isa_vs_parent": "instruction stream identical up to the symbol name and block labels "
+                                             "(2074 lines); the kernarg segment grew by one unused pointer"},
+    "scheduled_instantiation": {"vgpr_count": 237, "sgpr_spill_count": 67, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 0, "occupancy_waves_per_simd": 2},
+}
+
+
+def _time_ensembles(make, sizes, steps, reps):
+    """Median / min / max wall time of solve(steps) over `reps` fresh ensembles per size, after a warm-up."""
+    rows = []
+    for n_bars in sizes:
+        warm = make(n_bars)
+        warm.solve(5)
+        warm.close()
+        walls, its = [], 0.0
+        for _ in range(reps):
+            ens = make(n_bars)
+            t0 = time.perf_counter()
+            ens.solve(steps)  # returns after the device has finished
+            walls.append(time.perf_counter() - t0)
+            assert not ens.failed_step.any()
+            its = float(ens.newton_total.mean()) / steps
+            ens.close()
+        med = statistics.median(walls)
+        rows.append({"n_bars": n_bars, "wall_s": med, "wall_s_min": min(walls), "wall_s_max": max(walls),
+                     "spread": (max(walls) - min(walls)) / med, "newton_its_per_step": its})
+    return rows
+
+
+def scheduled_bench(args):
+    from geometry import graded_bar
+    from main import model_params
+    from tvfem import ThermoViscoEnsemble
+
+    mesh = graded_bar()
+    n_nodes = mesh.num_vertices
+    span = (0.0, args.steps * 0.1)
+
+    def plain(n_bars):
+        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFG, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)))
+        ens.setup()
+        return ens
+
+    def scheduled(n_bars):
+        quench_end = np.round(np.linspace(20.0, 100.0, n_bars)).astype(int)
+        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFG, dict(model_params), n_bars=n_bars,
+                                  schedule=[dict(until_step=quench_end, htc=900.0), dict(htc=60.0)],
+                                  history=dict(nodes=[0, (n_nodes - 1) // 2, n_nodes - 1], every=10))
+        ens.setup()
+        return ens
+
+    def neutral(n_bars):  # the unscheduled physics through the scheduled kernel: what the instantiation costs
+        htc = np.linspace(50.0, 1000.0, n_bars)
+        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFG, dict(model_params, htc=htc), schedule=[dict(htc=htc)],
+                                  history=dict(nodes=[0, (n_nodes - 1) // 2, n_nodes - 1], every=10))
+        ens.setup()
+        return ens
+
+    parent = None
+    if args.parent_tree:  # the parent commit's own tool, package and library, in a process of its own
+        tmp = os.path.join(tempfile.mkdtemp(), "parent.json")
+        cmd = [sys.executable, os.path.join(os.path.abspath(args.parent_tree), "tools", "ensemble_bench.py"),
+               "--steps", str(args.steps), "--reps", str(args.reps), "--seq-bars", "1", "--out", tmp,
+               "--sizes"] + [str(n) for n in args.sizes]
+        env = {k: v for k, v in os.environ.items() if k not in ("TVFEM_LIB", "PYTHONPATH")}
+        subprocess.run(cmd, env=env, check=True, stdout=subprocess.DEVNULL)
+        with open(tmp) as fh:
+            parent = json.load(fh)["ensemble"]
+        for r in parent:
+            r["spread"] = (r["wall_s_max"] - r["wall_s_min"]) / r["wall_s"]
+    new_plain = _time_ensembles(plain, args.sizes, args.steps, args.reps)
+    new_sched = _time_ensembles(scheduled, args.sizes, args.steps, args.reps)
+    new_neutral = _time_ensembles(neutral, args.sizes, args.steps, args.reps)
+    rows = []
+    for i, n_bars in enumerate(args.sizes):
+        row = {"n_bars": n_bars, "unscheduled": new_plain[i], "scheduled": new_sched[i],
+               "scheduled_over_unscheduled": new_sched[i]["wall_s"] / new_plain[i]["wall_s"],
+               "one_stage_own_values_with_history": new_neutral[i],
+               "one_stage_own_values_over_unscheduled": new_neutral[i]["wall_s"] / new_plain[i]["wall_s"]}
+        line = (f"{n_bars:6d} bars: unscheduled {new_plain[i]['wall_s'] * 1e3:8.2f} ms "
+                f"({new_plain[i]['newton_its_per_step']:.3f} its)  "
+                f"scheduled {new_sched[i]['wall_s'] * 1e3:8.2f} ms ({new_sched[i]['newton_its_per_step']:.3f} its)  "
+                f"one stage, own values {new_neutral[i]['wall_s'] * 1e3:8.2f} ms")
+        if parent:
+            base = parent[i]["wall_s"]
+            row["parent_unscheduled"] = parent[i]
+            row["margin"] = max(0.02, 3.0 * parent[i]["spread"])
+            row["unscheduled_over_parent"] = new_plain[i]["wall_s"] / base
+            row["scheduled_over_parent"] = new_sched[i]["wall_s"] / base
+            row["within_margin"] = {"unscheduled": row["unscheduled_over_parent"] <= 1.0 + row["margin"],
+                                    "scheduled": row["scheduled_over_parent"] <= 1.0 + row["margin"]}
+            line += (f"  parent {base * 1e3:8.2f} ms (spread {parent[i]['spread']:.2%})  ratios "
+                     f"{row['unscheduled_over_parent']:.4f} / {row['scheduled_over_parent']:.4f}  "
+                     f"margin {row['margin']:.2%}")
+        rows.append(row)
+        print(line, flush=True)
+    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "steps": args.steps, "dt": 0.1,
+                        "families": "CG1/CG1", "reps": args.reps,
+                        "unscheduled": "htc linspace(50, 1000, n_bars), as ensemble_bench.json",
+                        "scheduled": "two stages, quench end per bar linspace(20, 100, n_bars) steps, htc 900 -> 60, "
+                                     "probes at the two surfaces and the mid-plane, every 10 steps"},
+           "parent": "the parent commit's own checkout and tool, child process of the same session"
+                     if parent else None,
+           "kernel": KERNEL_RECORD, "sizes": rows}
+    out = args.out or os.path.join(ROOT, "profiles", "ensemble_schedule_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps({"out": out}))
 
 
 def main():
@@ -57,8 +184,15 @@ def main():
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seq-bars", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ensemble_bench.json"))
+    ap.add_argument("--out", default=None, help="default profiles/ensemble_bench.json "
+                                                "(--scheduled: profiles/ensemble_schedule_bench.json)")
+    ap.add_argument("--scheduled", action="store_true", help="the cost of a schedule and a history (see above)")
+    ap.add_argument("--parent-tree", default=None,
+                    help="--scheduled: a built checkout of the parent commit; its own tools/ensemble_bench.py runs")
     args = ap.parse_args()
+    if args.scheduled:
+        return scheduled_bench(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "ensemble_bench.json")
 
     from geometry import graded_bar
     from main import model_params
