@@ -306,7 +306,7 @@ Csr spgemm(const Csr& A, const Csr& B) {
 template <class T>
 int amg_alloc(Ctx* c, size_t n, T** out) {
   void* p = nullptr;
-  HIPC(hipMalloc(&p, sizeof(T) * std::max<size_t>(1, n)));
+  HIPC(tv_dev_alloc(&p, sizeof(T) * std::max<size_t>(1, n), mem_kind<T>()));
   c->amg_bufs.push_back(p);
   *out = static_cast<T*>(p);
   return TV_OK;
@@ -609,7 +609,7 @@ static int amg_build(Ctx* c, Csr A, int64_t row0, int64_t nrow, const int64_t* g
     A = std::move(Ac);
   }
   if (c->amg.empty()) return c->fail(TV_ERR_ARG, "AMG: the mesh is too small to coarsen");
-  HIPC(hipMalloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
+  HIPC(tv_dev_alloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
   HIPC(hipMemset(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
   c->amg_on = true;
   c->mg_on = true;
@@ -646,9 +646,9 @@ int amg_setup_part(Ctx* c) {
   hipStream_t s = c->stream;
   double* dv = nullptr;
   auto dev = [&](size_t n) -> int {
-    if (dv) HIPC(hipFree(dv));
+    if (dv) HIPC(tv_dev_free(dv));
     dv = nullptr;
-    HIPC(hipMalloc(&dv, sizeof(double) * std::max<size_t>(1, n)));
+    HIPC(tv_dev_alloc(&dv, sizeof(double) * std::max<size_t>(1, n), kMemDoubles));
     return TV_OK;
   };
   auto run = [&]() -> int {
@@ -711,12 +711,12 @@ int amg_setup_part(Ctx* c) {
     A.col.resize((size_t)nnz);
     A.val.swap(vv);
     for (int64_t k = 0; k < nnz; ++k) A.col[(size_t)k] = (int)cv[(size_t)k];
-    if (dv) HIPC(hipFree(dv));
+    if (dv) HIPC(tv_dev_free(dv));
     dv = nullptr;
     return amg_build(c, std::move(A), off, nown);
   };
   const int e = run();
-  if (dv) hipFree(dv);
+  if (dv) tv_dev_free(dv);
   return e;
 }
 

@@ -25,7 +25,7 @@ int refresh_dirty_ghosts(Ctx* c) {
   // T and T_prev are exchanged every step anyway (newton); the other fields
   // only when a rank wrote them.  Every rank learns the union of the writes
   // through one all-reduce of a flag per field.
-  if (!c->d_dirty) HIPC(hipMalloc(&c->d_dirty, sizeof(double) * TV_NUM_FIELDS));
+  if (!c->d_dirty) HIPC(tv_dev_alloc(&c->d_dirty, sizeof(double) * TV_NUM_FIELDS, kMemDoubles));
   double fl[TV_NUM_FIELDS];
   for (int f = 0; f < TV_NUM_FIELDS; ++f) fl[f] = (c->ghost_dirty >> f) & 1u ? 1.0 : 0.0;
   HIPC(hipMemcpyAsync(c->d_dirty, fl, sizeof(fl), hipMemcpyHostToDevice, c->stream));
@@ -235,7 +235,7 @@ int halo_dg(Ctx* c, double* v) {
     if (hi) HIPC(hipMemsetAsync(v + g.gofs[1], 0, L * sizeof(double), c->stream));
     return TV_OK;
   }
-  if (!c->dg_sbuf) HIPC(hipMalloc(&c->dg_sbuf, sizeof(double) * 2 * (size_t)L));
+  if (!c->dg_sbuf) HIPC(tv_dev_alloc(&c->dg_sbuf, sizeof(double) * 2 * (size_t)L, kMemDoubles));
   const int nb = (int)std::min<int64_t>(1024, (2 * L + kBlock - 1) / kBlock);
   hipLaunchKernelGGL(k_dg_pack, dim3(nb), dim3(kBlock), 0, c->stream, v, g.own, pc, nl,
                      (int64_t)(g.k_end - g.k_begin - 1) * pc, c->dg_sbuf);
@@ -421,8 +421,8 @@ int comm_check(Ctx* c, int64_t* n_chk, int64_t* n_bad) {
   double* v = nullptr;
   double* s = nullptr;
   double* ff = nullptr;
-  HIPC(hipMalloc(&v, sizeof(double) * (size_t)nmax));
-  HIPC(hipMalloc(&s, sizeof(double) * 4));
+  HIPC(tv_dev_alloc(&v, sizeof(double) * (size_t)nmax, kMemDoubles));
+  HIPC(tv_dev_alloc(&s, sizeof(double) * 4, kMemDoubles));
   std::vector<double> h((size_t)nmax);
   auto sums_ok = [&](const double* d, int n, const double* want) -> int {
     double hs[4];
@@ -529,7 +529,7 @@ int comm_check(Ctx* c, int64_t* n_chk, int64_t* n_bad) {
     }
     // 3. cgs_exchange: the single-reduction iteration's group (facet terms zero)
     if (c->cgs && c->wsend) {
-      HIPC(hipMalloc(&ff, sizeof(double) * (size_t)std::max<int64_t>(1, g.ffsize)));
+      HIPC(tv_dev_alloc(&ff, sizeof(double) * (size_t)std::max<int64_t>(1, g.ffsize), kMemDoubles));
       HIPC(hipMemsetAsync(ff, 0, sizeof(double) * (size_t)std::max<int64_t>(1, g.ffsize), c->stream));
       if (int e = fill_ids(c, g, v, first)) return e;
       const double hs[3] = {(double)(c->rank + 1), 1.0, 2.0};
@@ -565,9 +565,9 @@ int comm_check(Ctx* c, int64_t* n_chk, int64_t* n_bad) {
   };
   const int e = run();
   hipStreamSynchronize(c->stream);
-  hipFree(v);
-  hipFree(s);
-  if (ff) hipFree(ff);
+  tv_dev_free(v);
+  tv_dev_free(s);
+  if (ff) tv_dev_free(ff);
   return e;
 }
 

@@ -65,7 +65,7 @@ int alloc_field(Ctx* c, int id, int space, int bs) {
   // the fused visco update streams ~26 fields at the same index at once, and
   // page-aligned starts put all of them on the same HBM channels together
   const size_t stagger = (size_t)(id % 15) * (132u << 10);
-  HIPC(hipMalloc(&fi.base, sizeof(double) * (size_t)std::max<int64_t>(1, n * bs) + stagger));
+  HIPC(tv_dev_alloc(&fi.base, sizeof(double) * (size_t)std::max<int64_t>(1, n * bs) + stagger, kMemDoubles));
   fi.ptr = reinterpret_cast<double*>(static_cast<char*>(fi.base) + stagger);
   HIPC(hipMemsetAsync(fi.ptr, 0, sizeof(double) * (size_t)(n * bs), c->stream));
   fi.alloc = true;
@@ -127,7 +127,7 @@ int build_cg_grid(Ctx* c, int d, const std::vector<double> (&X)[3], int first2, 
   for (int s = 0; s < 3; ++s) {
     std::vector<double> cf;
     axis_coefs(X[s], first[s], cnt[s], cf);
-    HIPC(hipMalloc(&coef[s], cf.size() * sizeof(double)));
+    HIPC(tv_dev_alloc(&coef[s], cf.size() * sizeof(double), kMemDoubles));
     HIPC(hipMemcpy(coef[s], cf.data(), cf.size() * sizeof(double), hipMemcpyHostToDevice));
     g.coef[s] = coef[s];
   }
@@ -144,7 +144,7 @@ int build_cg_grid(Ctx* c, int d, const std::vector<double> (&X)[3], int first2, 
           if (on) bn.push_back((int64_t)i + (int64_t)g.n0 * j + plane * k);
         }
     if (!bn.empty()) {
-      HIPC(hipMalloc(bnodes, bn.size() * sizeof(int64_t)));
+      HIPC(tv_dev_alloc(bnodes, bn.size() * sizeof(int64_t), kMemOther));
       HIPC(hipMemcpy(*bnodes, bn.data(), bn.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     g.bnodes = *bnodes;
@@ -167,7 +167,7 @@ int build_cg_grid(Ctx* c, int d, const std::vector<double> (&X)[3], int first2, 
     }
     g.ffsize = tot;
     for (int q = 0; q < 2; ++q) {
-      HIPC(hipMalloc(&ffbuf[q], sizeof(double) * (size_t)std::max<int64_t>(1, tot)));
+      HIPC(tv_dev_alloc(&ffbuf[q], sizeof(double) * (size_t)std::max<int64_t>(1, tot), kMemDoubles));
       HIPC(hipMemsetAsync(ffbuf[q], 0, sizeof(double) * (size_t)std::max<int64_t>(1, tot), c->stream));
       g.ffbuf[q] = ffbuf[q];
     }
@@ -266,7 +266,7 @@ int setup_mixed_part(Ctx* c) {
       }
     }
   }
-  HIPC(hipMalloc(&c->map, sizeof(int) * (size_t)std::max<int64_t>(1, c->nS)));
+  HIPC(tv_dev_alloc(&c->map, sizeof(int) * (size_t)std::max<int64_t>(1, c->nS), kMemOther));
   HIPC(hipMemcpy(c->map, map.data(), sizeof(int) * (size_t)c->nS, hipMemcpyHostToDevice));
   return TV_OK;
 }
@@ -373,7 +373,7 @@ int setup_mesh(Ctx* c, const tv_mesh_desc* m) {
       else for (size_t i = 0; i + 1 < X.size(); ++i) h.push_back(X[i + 1] - X[i]);
       const size_t nh = h.size();
       for (size_t q = 0; q < nh; ++q) h.push_back(1.0 / h[q]);  // [h..., 1/h...]
-      HIPC(hipMalloc(&c->dgh[s], h.size() * sizeof(double)));
+      HIPC(tv_dev_alloc(&c->dgh[s], h.size() * sizeof(double), kMemDoubles));
       HIPC(hipMemcpy(c->dgh[s], h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
       g.h[s] = c->dgh[s];
       g.ih[s] = c->dgh[s] + nh;
@@ -425,7 +425,7 @@ int setup_mesh(Ctx* c, const tv_mesh_desc* m) {
         else map[(size_t)dgdof] = (int)node;                    // sigma DG <- T CG
       }
     }
-    HIPC(hipMalloc(&c->map, sizeof(int) * (size_t)c->nS));
+    HIPC(tv_dev_alloc(&c->map, sizeof(int) * (size_t)c->nS, kMemOther));
     HIPC(hipMemcpy(c->map, map.data(), sizeof(int) * (size_t)c->nS, hipMemcpyHostToDevice));
   }
   // thermal constants
@@ -467,7 +467,7 @@ int setup_fields(Ctx* c) {
     alias_field(c, TV_F_S_PARTIAL_NEXT, TV_F_S_PARTIAL);
     alias_field(c, TV_F_SIGMA_PARTIAL_NEXT, TV_F_SIGMA_PARTIAL);
   }
-  if (paper && c->fam_T != c->fam_S) HIPC(hipMalloc(&c->Tfo, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
+  if (paper && c->fam_T != c->fam_S) HIPC(tv_dev_alloc(&c->Tfo, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
   if (all) {
     AF(TV_F_T_NEXT, 0, 1);
     AF(TV_F_PHI_NEXT, 0, 1);
@@ -488,12 +488,12 @@ int setup_fields(Ctx* c) {
   alias_field(c, TV_F_SIGMA_TILDE_NEXT, TV_F_SIGMA_TILDE);
   // PCG work vectors (T space, local size)
   const size_t nb = sizeof(double) * (size_t)std::max<int64_t>(1, c->nT);
-  HIPC(hipMalloc(&c->r, nb));
-  HIPC(hipMalloc(&c->z, nb));
-  HIPC(hipMalloc(&c->pA, nb));
-  HIPC(hipMalloc(&c->pB, nb));
-  HIPC(hipMalloc(&c->w, nb));
-  HIPC(hipMalloc(&c->dinv, nb));
+  HIPC(tv_dev_alloc(&c->r, nb, kMemDoubles));
+  HIPC(tv_dev_alloc(&c->z, nb, kMemDoubles));
+  HIPC(tv_dev_alloc(&c->pA, nb, kMemDoubles));
+  HIPC(tv_dev_alloc(&c->pB, nb, kMemDoubles));
+  HIPC(tv_dev_alloc(&c->w, nb, kMemDoubles));
+  HIPC(tv_dev_alloc(&c->dinv, nb, kMemDoubles));
   for (double* p : {c->r, c->z, c->pA, c->pB, c->w, c->dinv}) HIPC(hipMemsetAsync(p, 0, nb, c->stream));
   c->f[TV_F_RESIDUAL].ptr = c->r; c->f[TV_F_RESIDUAL].bs = 1; c->f[TV_F_RESIDUAL].space = 0;
   if (int e = alloc_field(c, TV_F_DX, 0, 1)) return e;
@@ -503,15 +503,15 @@ int setup_fields(Ctx* c) {
   else np = std::max(np, dg_num_blocks(c->dg));
   c->n_partials_cap = np;
   // records of width <= 3 per workgroup + the shard records of the two-level tail
-  HIPC(hipMalloc(&c->partials, sizeof(double) * 3 * ((size_t)np + 2 * kShards)));
-  HIPC(hipMalloc(&c->sums, sizeof(double) * 8));
-  HIPC(hipMalloc(&c->ngate, sizeof(double) * 8));
+  HIPC(tv_dev_alloc(&c->partials, sizeof(double) * 3 * ((size_t)np + 2 * kShards), kMemDoubles));
+  HIPC(tv_dev_alloc(&c->sums, sizeof(double) * 8, kMemDoubles));
+  HIPC(tv_dev_alloc(&c->ngate, sizeof(double) * 8, kMemDoubles));
   HIPC(hipMemset(c->ngate, 0, sizeof(double) * 8));
   if (const char* e = std::getenv("TVFEM_NEWTON_AHEAD")) c->newton_ahead = std::atoi(e) != 0;
-  HIPC(hipMalloc(&c->counters, sizeof(unsigned) * kCounterWords));
+  HIPC(tv_dev_alloc(&c->counters, sizeof(unsigned) * kCounterWords, kMemOther));
   HIPC(hipMemsetAsync(c->counters, 0, sizeof(unsigned) * kCounterWords, c->stream));
-  HIPC(hipMalloc(&c->st, sizeof(PcgState)));
-  HIPC(hipMalloc(&c->tflag, sizeof(int)));
+  HIPC(tv_dev_alloc(&c->st, sizeof(PcgState), kMemOther));
+  HIPC(tv_dev_alloc(&c->tflag, sizeof(int), kMemOther));
   HIPC(hipMemsetAsync(c->tflag, 0, sizeof(int), c->stream));  // the tilde fields start at +0.0
   HIPC(hipHostMalloc(&c->h_st, 3 * sizeof(PcgState)));
   for (int k = 0; k < 2; ++k) HIPC(hipEventCreateWithFlags(&c->evp[k], hipEventDisableTiming));
@@ -551,11 +551,11 @@ int setup_fields(Ctx* c) {
                     c->O.preconditioner != TV_PC_GMG));  // the multigrid solve runs in the KSPCG form
   if (c->cgs) {
     for (double** q : {&c->cr[0], &c->cr[1], &c->cs[0], &c->cs[1], &c->cw1}) {
-      HIPC(hipMalloc(q, nb));
+      HIPC(tv_dev_alloc(q, nb, kMemDoubles));
       HIPC(hipMemsetAsync(*q, 0, nb, c->stream));
     }
     const size_t plane = (size_t)c->cg.n0 * c->cg.n1;
-    HIPC(hipMalloc(&c->wsend, sizeof(double) * 2 * plane));
+    HIPC(tv_dev_alloc(&c->wsend, sizeof(double) * 2 * plane, kMemDoubles));
   }
   return TV_OK;
 }
@@ -592,9 +592,9 @@ int transfer(Ctx* c, int field, double* host, size_t n, int dir) {
   const int64_t ncell = dgsp ? ndof / nl : 0;
   const size_t bytes = need * sizeof(double);
   if (c->scratch_bytes < bytes) {
-    if (c->scratch) HIPC(hipFree(c->scratch));
+    if (c->scratch) HIPC(tv_dev_free(c->scratch));
     c->scratch = nullptr;
-    HIPC(hipMalloc(&c->scratch, std::max<size_t>(bytes, 8)));
+    HIPC(tv_dev_alloc(&c->scratch, std::max<size_t>(bytes, 8), kMemDoubles));
     c->scratch_bytes = bytes;
   }
   const int blocks = (int)std::min<int64_t>(std::max<int64_t>(1, ((int64_t)need + 255) / 256), 16384);
@@ -788,9 +788,9 @@ static int setup_umesh(Ctx* c, const tv_umesh_desc* m, const tv_upart_desc* pd) 
       if (pd->send_idx[k] < 0 || pd->send_idx[k] >= nown)
         return c->fail(TV_ERR_ARG, "tv_upart_desc: send_idx must name owned vertices");
     if (stot > 0) {
-      HIPC(hipMalloc(&c->um_sidx, sizeof(int64_t) * (size_t)stot));
+      HIPC(tv_dev_alloc(&c->um_sidx, sizeof(int64_t) * (size_t)stot, kMemOther));
       HIPC(hipMemcpy(c->um_sidx, pd->send_idx, sizeof(int64_t) * (size_t)stot, hipMemcpyHostToDevice));
-      HIPC(hipMalloc(&c->um_sbuf, sizeof(double) * (size_t)stot));
+      HIPC(tv_dev_alloc(&c->um_sbuf, sizeof(double) * (size_t)stot, kMemDoubles));
     }
     c->n_parts = pd->n_parts;
     c->part = pd->part;
@@ -812,7 +812,7 @@ static int setup_umesh(Ctx* c, const tv_umesh_desc* m, const tv_upart_desc* pd) 
     return c->fail(err.rfind("HIP", 0) == 0 ? TV_ERR_HIP : TV_ERR_ARG, err);
   std::vector<unsigned char> bm;
   um_boundary_vertices(c->umd, bm);
-  HIPC(hipMalloc(&c->um_bmask, bm.size()));
+  HIPC(tv_dev_alloc(&c->um_bmask, bm.size(), kMemOther));
   HIPC(hipMemcpy(c->um_bmask, bm.data(), bm.size(), hipMemcpyHostToDevice));
   c->nT = c->nS = g.nv;
   c->ownT_off = c->ownS_off = 0;
@@ -943,46 +943,46 @@ int tv_destroy(void* ctx) {
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->out) output_destroy(c->out);
   for (int i = 0; i < TV_NUM_FIELDS; ++i)
-    if (c->f[i].alloc && c->f[i].base) hipFree(c->f[i].base);
+    if (c->f[i].alloc && c->f[i].base) tv_dev_free(c->f[i].base);
   for (double* p : {c->cr[0], c->cr[1], c->cs[0], c->cs[1], c->cw1, c->wsend, c->dB, c->dtmp, c->Tfo})
-    if (p) hipFree(p);
+    if (p) tv_dev_free(p);
   um_free(c->umd);
-  if (c->um_bmask) hipFree(c->um_bmask);
-  if (c->um_sidx) hipFree(c->um_sidx);
-  for (void* p : c->amg_bufs) hipFree(p);
-  if (c->um_sbuf) hipFree(c->um_sbuf);
+  if (c->um_bmask) tv_dev_free(c->um_bmask);
+  if (c->um_sidx) tv_dev_free(c->um_sidx);
+  for (void* p : c->amg_bufs) tv_dev_free(p);
+  if (c->um_sbuf) tv_dev_free(c->um_sbuf);
   for (MgLevel& L : c->mg) {
-    for (void* p : L.bufs) hipFree(p);
+    for (void* p : L.bufs) tv_dev_free(p);
     for (int s = 0; s < 3; ++s)
-      if (L.coef[s]) hipFree(L.coef[s]);
-    if (L.bnodes) hipFree(L.bnodes);
+      if (L.coef[s]) tv_dev_free(L.coef[s]);
+    if (L.bnodes) tv_dev_free(L.bnodes);
     for (int q = 0; q < 2; ++q)
-      if (L.ffbuf[q]) hipFree(L.ffbuf[q]);
-    if (L.mask) hipFree(L.mask);
+      if (L.ffbuf[q]) tv_dev_free(L.ffbuf[q]);
+    if (L.mask) tv_dev_free(L.mask);
   }
-  if (c->mgx) hipFree(c->mgx);
-  if (c->mg_s) hipFree(c->mg_s);
-  if (c->dggface) hipFree(c->dggface);
+  if (c->mgx) tv_dev_free(c->mgx);
+  if (c->mg_s) tv_dev_free(c->mg_s);
+  if (c->dggface) tv_dev_free(c->dggface);
   for (double* p : {c->r, c->z, c->pA, c->pB, c->w, c->dinv, c->partials, c->sums, c->ngate, c->scratch})
-    if (p) hipFree(p);
+    if (p) tv_dev_free(p);
   for (int s = 0; s < 3; ++s) {
-    if (c->coef[s]) hipFree(c->coef[s]);
-    if (c->dgh[s]) hipFree(c->dgh[s]);
+    if (c->coef[s]) tv_dev_free(c->coef[s]);
+    if (c->dgh[s]) tv_dev_free(c->dgh[s]);
   }
-  if (c->map) hipFree(c->map);
-  if (c->bnodes) hipFree(c->bnodes);
+  if (c->map) tv_dev_free(c->map);
+  if (c->bnodes) tv_dev_free(c->bnodes);
   for (int q = 0; q < 2; ++q)
-    if (c->ffbuf[q]) hipFree(c->ffbuf[q]);
-  if (c->st) hipFree(c->st);
-  if (c->tflag) hipFree(c->tflag);
-  if (c->counters) hipFree(c->counters);
+    if (c->ffbuf[q]) tv_dev_free(c->ffbuf[q]);
+  if (c->st) tv_dev_free(c->st);
+  if (c->tflag) tv_dev_free(c->tflag);
+  if (c->counters) tv_dev_free(c->counters);
   if (c->h_st) hipHostFree(c->h_st);
   if (c->h_sums) hipHostFree(c->h_sums);
-  if (c->d_dirty) hipFree(c->d_dirty);
-  if (c->dg_sbuf) hipFree(c->dg_sbuf);
+  if (c->d_dirty) tv_dev_free(c->d_dirty);
+  if (c->dg_sbuf) tv_dev_free(c->dg_sbuf);
   if (c->h_halo) hipHostFree(c->h_halo);
   if (c->h_big) hipHostFree(c->h_big);
-  if (c->mg_mask0) hipFree(c->mg_mask0);
+  if (c->mg_mask0) tv_dev_free(c->mg_mask0);
   if (c->comm) ncclCommDestroy(c->comm);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
@@ -992,7 +992,7 @@ int tv_destroy(void* ctx) {
   }
   for (hipEvent_t e : c->evn)
     if (e) hipEventDestroy(e);
-  if (c->d_ts) hipFree(c->d_ts);
+  if (c->d_ts) tv_dev_free(c->d_ts);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
   return TV_OK;
@@ -1254,8 +1254,8 @@ int tv_set_dirichlet(void* ctx, int enable, double value) {
   c->dir_value = value;
   if (c->dir_on && c->fam_T == TV_CG && !c->dB) {
     const size_t nb = sizeof(double) * (size_t)std::max<int64_t>(1, c->nT);
-    HIPC(hipMalloc(&c->dB, nb));
-    HIPC(hipMalloc(&c->dtmp, nb));
+    HIPC(tv_dev_alloc(&c->dB, nb, kMemDoubles));
+    HIPC(tv_dev_alloc(&c->dtmp, nb, kMemDoubles));
     HIPC(hipMemsetAsync(c->dtmp, 0, nb, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
   }

@@ -363,11 +363,11 @@ void mg_axis_tables(const std::vector<double>& Xf, const std::vector<char>& is_c
 int mg_level_vectors(Ctx* c, MgLevel& L);
 double mg_gershgorin(const std::vector<double> (&X)[3], double dt_alpha);
 double mg_omega(double b);
-void mg_level(Ctx* c, size_t l);
+int mg_level(Ctx* c, size_t l);  // a status
 template <class T>
 int mg_upload(Ctx* c, MgLevel& L, const std::vector<T>& h, const T** out) {
   void* p = nullptr;
-  HIPC(hipMalloc(&p, sizeof(T) * std::max<size_t>(1, h.size())));
+  HIPC(tv_dev_alloc(&p, sizeof(T) * std::max<size_t>(1, h.size()), mem_kind<T>()));
   L.bufs.push_back(p);
   HIPC(hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
   *out = static_cast<const T*>(p);

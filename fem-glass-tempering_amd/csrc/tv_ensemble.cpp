@@ -56,8 +56,8 @@ const char* ensemble_last_error(const void* h) {
 
 namespace {
 
-int ens_alloc(Ens* c, size_t bytes, void** out) {
-  HIPC(hipMalloc(out, bytes));
+int ens_alloc(Ens* c, size_t bytes, void** out, int kind = kMemDoubles) {
+  HIPC(tv_dev_alloc(out, bytes, kind));
   c->bufs.push_back(*out);
   HIPC(hipMemsetAsync(*out, 0, bytes, c->stream));
   return TV_OK;
@@ -102,7 +102,7 @@ int ens_transfer(Ens* c, int field, double* host, size_t n_values, bool to_devic
 int ens_push_ext(Ens* c) {
   if (!c->dx) {
     void* p = nullptr;
-    if (int e = ens_alloc(c, sizeof(EnsExt), &p)) return e;
+    if (int e = ens_alloc(c, sizeof(EnsExt), &p, kMemOther)) return e;
     c->dx = static_cast<EnsExt*>(p);
   }
   HIPC(hipMemcpyAsync(c->dx, &c->x, sizeof(EnsExt), hipMemcpyHostToDevice, c->stream));
@@ -196,9 +196,9 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   if (rc == TV_OK) rc = ens_alloc(c.get(), par.size() * sizeof(double), &dpar);
   if (rc == TV_OK) rc = ens_alloc(c.get(), cell.size() * sizeof(double), &dcell);
   if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(double) * 2 * n * pad, &scr);
-  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &its);
-  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &fs);
-  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int64_t) * pad, &tot);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &its, kMemOther);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &fs, kMemOther);
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int64_t) * pad, &tot, kMemOther);
   auto upload = [&](void* dst, const std::vector<double>& src) {
     HIPC(hipMemcpyAsync(dst, src.data(), src.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
@@ -208,7 +208,7 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   if (rc == TV_OK) rc = upload(dcell, cell);
   if (rc != TV_OK) {
     set_global_error(c->err);
-    for (void* p : c->bufs) hipFree(p);
+    for (void* p : c->bufs) tv_dev_free(p);
     hipStreamDestroy(c->stream);
     return rc;
   }
@@ -270,9 +270,9 @@ int tv_ensemble_destroy(void* ens) {
   }
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  for (void* p : c->bufs) hipFree(p);
-  hipFree(c->sched_buf);
-  hipFree(c->hist_buf);
+  for (void* p : c->bufs) tv_dev_free(p);
+  tv_dev_free(c->sched_buf);
+  tv_dev_free(c->hist_buf);
   hipStreamDestroy(c->stream);
   delete c;
   return TV_OK;
@@ -372,7 +372,7 @@ int tv_ensemble_set_schedule(void* ens, const tv_ensemble_schedule* s) {
   if (!c) return TV_ERR_ARG;
   hipSetDevice(c->device);
   if (!s) {  // back to the creation values
-    hipFree(c->sched_buf);  // no launch is in flight: tv_ensemble_step returns after its launches
+    tv_dev_free(c->sched_buf);  // no launch is in flight: tv_ensemble_step returns after its launches
     c->sched_buf = nullptr;
     c->x.n_stages = 0;
     c->x.stage_end = nullptr;
@@ -428,17 +428,17 @@ int tv_ensemble_set_schedule(void* ens, const tv_ensemble_schedule* s) {
     for (; row < nst; ++row) put(last, INT32_MAX);
   }
   void* buf = nullptr;
-  HIPC(hipMalloc(&buf, val.size() * sizeof(double) + end.size() * sizeof(int)));
+  HIPC(tv_dev_alloc(&buf, val.size() * sizeof(double) + end.size() * sizeof(int), kMemOther));
   double* dval = static_cast<double*>(buf);
   int* dend = reinterpret_cast<int*>(dval + val.size());
   hipError_t e1 = hipMemcpyAsync(dval, val.data(), val.size() * sizeof(double), hipMemcpyHostToDevice, c->stream);
   hipError_t e2 = hipMemcpyAsync(dend, end.data(), end.size() * sizeof(int), hipMemcpyHostToDevice, c->stream);
   hipError_t e3 = hipStreamSynchronize(c->stream);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-    hipFree(buf);
+    tv_dev_free(buf);
     return c->fail(TV_ERR_HIP, "tv_ensemble_set_schedule: upload failed");
   }
-  hipFree(c->sched_buf);
+  tv_dev_free(c->sched_buf);
   c->sched_buf = buf;
   c->x.n_stages = nst;
   c->x.stage_end = dend;
@@ -456,7 +456,7 @@ int tv_ensemble_history_open(void* ens, int n_probes, const int* dofs, int every
   auto bad = [&](const std::string& m) { return c->fail(TV_ERR_ARG, "tv_ensemble_history_open: " + m); };
   if (n_probes < 0) return bad("n_probes is negative");
   if (n_probes == 0) {  // close: the records go, the step cap with them
-    hipFree(c->hist_buf);
+    tv_dev_free(c->hist_buf);
     c->hist_buf = nullptr;
     c->x.n_probes = 0;
     c->x.every = 1;
@@ -477,7 +477,7 @@ int tv_ensemble_history_open(void* ens, int n_probes, const int* dofs, int every
   if ((double)max_records * 3.0 * n_probes * (double)pad > (double)(INT64_C(1) << 37)) return bad("history too large");
   const size_t n_val = (size_t)max_records * 3 * n_probes * pad;
   void* buf = nullptr;
-  HIPC(hipMalloc(&buf, n_val * sizeof(double) + (size_t)n_probes * sizeof(int)));
+  HIPC(tv_dev_alloc(&buf, n_val * sizeof(double) + (size_t)n_probes * sizeof(int), kMemOther));
   double* dh = static_cast<double*>(buf);
   int* dprobes = reinterpret_cast<int*>(dh + n_val);
   // all bits set is a NaN: what a record reads until its step has written it
@@ -485,10 +485,10 @@ int tv_ensemble_history_open(void* ens, int n_probes, const int* dofs, int every
   hipError_t e2 = hipMemcpyAsync(dprobes, dofs, (size_t)n_probes * sizeof(int), hipMemcpyHostToDevice, c->stream);
   hipError_t e3 = hipStreamSynchronize(c->stream);
   if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
-    hipFree(buf);
+    tv_dev_free(buf);
     return c->fail(TV_ERR_HIP, "tv_ensemble_history_open: device setup failed");
   }
-  hipFree(c->hist_buf);
+  tv_dev_free(c->hist_buf);
   c->hist_buf = buf;
   c->x.n_probes = n_probes;
   c->x.every = every;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "tvfem.h"
@@ -13,6 +14,27 @@ namespace tv {
 constexpr int kWave = 64;         // CDNA wavefront
 constexpr int kSeg = kWave - 2;   // outputs per wave of the x-row stencil kernels
 constexpr int kBlock = 256;       // 4 waves
+
+// ---- device memory (tv_alloc.cpp) ----
+// Every device allocation of the library: the plain HIP allocation, or with
+// TVFEM_ALLOC_GUARD=<KiB> (read at each allocation) the same data between two
+// filled red zones that tv_guard_check compares with their fill.  kind = what
+// the allocation holds, which selects the fill: NaN bit patterns around
+// doubles, zeros around anything else (indices, flags, structs).
+enum { kMemDoubles = 0, kMemOther = 1 };
+template <class T>
+constexpr int mem_kind() {
+  return std::is_same<T, double>::value ? kMemDoubles : kMemOther;
+}
+hipError_t tv_dev_alloc(void** p, size_t bytes, int kind);
+hipError_t tv_dev_free(void* p);
+template <class T>
+inline hipError_t tv_dev_alloc(T** p, size_t bytes, int kind) {
+  void* q = nullptr;
+  const hipError_t e = tv_dev_alloc(&q, bytes, kind);
+  if (e == hipSuccess) *p = static_cast<T*>(q);
+  return e;
+}
 
 // Per-node coefficients of one storage axis of a rectilinear grid: the
 // assembled 1D P1 mass (lo, diag, up), 1D stiffness (lo, diag, up), and the
@@ -510,7 +532,10 @@ struct RRArgs {
   double da;           // dt alpha
   int raxis, nseg, qchunk;
 };
-void launch_mg_rrestrict(const RRArgs& a, const PcgState* st, const double* b, const double* x, const FaceAdd& fa,
+// false (nothing launched, the coarse vectors are stale): a march chunk outside
+// [1, kRRQMaxChunk], which rr_setup refuses -- the caller fails the solve
+constexpr int kRRQMaxChunk = 64;  // coarse march planes per chunk (the kernel's LDS weight stage)
+bool launch_mg_rrestrict(const RRArgs& a, const PcgState* st, const double* b, const double* x, const FaceAdd& fa,
                          double* bc, const double* dinv_c, double omega_c, double* xc, hipStream_t s);
 void launch_cg_facet_faces(const CgGrid& g, const double* T, const double* x, const PcgState* st, hipStream_t s);
 FaceAdd cg_face_add_all(const CgGrid& g);  // the facet terms of every physical face (fface[] of g)

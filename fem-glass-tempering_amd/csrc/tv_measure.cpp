@@ -141,8 +141,8 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
     switch (kernel) {
       case 11:  // partitioned: the distributed V-cycle, its exchanges included (every rank calls this)
         if (c->n_parts > 1) return mg_apply0_dist(c, c->f[TV_F_T].ptr, nullptr);
-        mg_apply0(c, c->f[TV_F_T].ptr, nullptr);
-        return TV_OK;
+        np = mg_apply0(c, c->f[TV_F_T].ptr, nullptr);
+        return np < 0 ? -np : TV_OK;
       case 0: jx(); return TV_OK;
       case 1: return visco(c, false);
       case 2: op_residual(c, c->f[TV_F_T].ptr, c->f[TV_F_T_PREV].ptr, c->r); return TV_OK;
@@ -253,7 +253,7 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
     // the first workgroup in a kernel trace).
     const size_t fl = (size_t)512 << 20;
     void* flush = nullptr;
-    HIPC(hipMalloc(&flush, fl));
+    HIPC(tv_dev_alloc(&flush, fl, kMemOther));
     std::vector<hipEvent_t> ev(2 * (size_t)reps);
     for (auto& e : ev) HIPC(hipEventCreate(&e));
     jx();  // warm-up
@@ -273,7 +273,7 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
       t[(size_t)i] = f;
     }
     for (auto& e : ev) hipEventDestroy(e);
-    HIPC(hipFree(flush));
+    HIPC(tv_dev_free(flush));
     std::sort(t.begin(), t.end());
     *ms = (reps & 1) ? t[(size_t)reps / 2] : 0.5 * (t[(size_t)reps / 2 - 1] + t[(size_t)reps / 2]);
     return TV_OK;
@@ -302,7 +302,7 @@ int tv_kernel_timing(void* ctx, int on) {
     HIPC(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device));
     if (khz <= 0) return c->fail(TV_ERR_HIP, "tv_kernel_timing: no device wall clock rate");
     c->ts_khz = (double)khz;
-    HIPC(hipMalloc(&c->d_ts, (size_t)4 * kTsCap * sizeof(uint64_t)));
+    HIPC(tv_dev_alloc(&c->d_ts, (size_t)4 * kTsCap * sizeof(uint64_t), kMemOther));
   }
   c->ts_pending.clear();
   c->ts_next = kTsCap;  // zeroes the stamps

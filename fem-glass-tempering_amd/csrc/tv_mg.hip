@@ -783,7 +783,7 @@ constexpr int kRRSeg = kWave - 2;
 constexpr int kRRWaves = 8;
 constexpr int kRRRows = 2 * kRRWaves + 3;          // fine rows per plane (coarsened row axis)
 constexpr int kRRPer = (kRRRows + kRRWaves - 1) / kRRWaves;  // rows loaded per wave
-constexpr int kRRQMax = 64;  // coarse march planes per chunk (LDS weight stage)
+constexpr int kRRQMax = kRRQMaxChunk;  // coarse march planes per chunk (LDS weight stage)
 constexpr int kRRPF = 1;     // fine planes of loads in flight ahead of the one reduced (2, 3: slower, profiles/r06_rrestrict_loads_ab.txt)
 
 // buffer resource of a level vector (32-bit byte offsets: a per-lane x offset in
@@ -801,6 +801,9 @@ __device__ __forceinline__ d2a8 rr_ld2(rr_buf r, uint32_t voff, uint32_t soff) {
   const u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0);
   return __builtin_bit_cast(d2a8, v);
 }
+// a pair loaded by the row's tail lane (k_mg_rrestrict: the pair ENDING at its
+// node) as the pair starting there: the node in .x, nothing (0) beyond the row
+__device__ __forceinline__ d2a8 rr_tail(d2a8 v, bool tail) { return tail ? d2a8{v.y, 0.0} : v; }
 __device__ __forceinline__ double rr_ld1(rr_buf r, uint32_t voff) {
   return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (int)voff, 0, 0));
 }
@@ -871,10 +874,18 @@ __global__ __launch_bounds__(kRRWaves * kWave) void k_mg_rrestrict(RRArgs a, con
   }
   const uint32_t nbytes = (uint32_t)a.fn[0] * (uint32_t)a.fn[1] * (uint32_t)a.fn[2] * 8u;
   const rr_buf rx = rr_rsrc(x, nbytes), rbv = rr_rsrc(b, nbytes);
-  // the lane's fine pair (e0, e0 + 1) straight from the row; the last lane's
-  // e0 + 1 is the next row's first node (weight 0), the lanes outside the axis
-  // carry an out-of-range offset (the range check returns 0)
-  const uint32_t voff = Iok ? (uint32_t)e0 * 8u : 0x40000000u;
+  // the lane's fine pair (e0, e0 + 1) straight from the row; the lanes outside
+  // the axis carry an out-of-range offset in voffset (the range check returns
+  // 0).  The row's last node e0 = nf0 - 1 (nf0 is odd, rr_setup) has no e0 + 1:
+  // on the last row of the last plane that pair would end one double past the
+  // vector, where only the range check stands between a weight 0 and whatever
+  // lies there (0 x NaN = NaN).  gfx950 applies the check to voffset + soffset,
+  // per dword (measured: profiles/guard_rrestrict_tail_ab.txt), but the
+  // intrinsic's contract leaves soffset out of it, so nothing here relies on
+  // that: the lane loads the pair ENDING at its node (always inside the row,
+  // as the tail lane of k_mg_restrict_pairs does) and rr_tail puts it in place.
+  const bool xtail = Iok && e0 == nf0 - 1;
+  const uint32_t voff = Iok ? (uint32_t)(e0 - (xtail ? 1 : 0)) * 8u : 0x40000000u;
   // facet terms: the x faces at the lanes holding fine x node 0 / nf0 - 1 (in
   // the waves that have one: loaded with the plane), the row-axis faces on the
   // axis' first / last row and the march-axis faces on the first / last fine
@@ -937,14 +948,15 @@ __global__ __launch_bounds__(kRRWaves * kWave) void k_mg_rrestrict(RRArgs a, con
     d2a8 sv[kRRPer];
 #pragma unroll
     for (int u = 0; u < kRRPer; ++u) {
-      sv[u] = S.bv[u];
+      sv[u] = rr_tail(S.bv[u], xtail);
       sv[u].x -= S.fx[u];
       if (u == uf) {  // a row-axis face row (wave-uniform)
-        sv[u].x -= S.fr.x;
-        sv[u].y -= S.fr.y;
+        const d2a8 f = rr_tail(S.fr, xtail);
+        sv[u].x -= f.x;
+        sv[u].y -= f.y;
       }
       if (qlo || qhi) {  // a march-axis face plane (face index i + n0 * row)
-        const d2a8 f = rr_ld2(qlo ? fql : fqh, voff, (uint32_t)(nf0 * frow[u]) * 8u);
+        const d2a8 f = rr_tail(rr_ld2(qlo ? fql : fqh, voff, (uint32_t)(nf0 * frow[u]) * 8u), xtail);
         sv[u].x -= f.x;
         sv[u].y -= f.y;
       }
@@ -952,7 +964,7 @@ __global__ __launch_bounds__(kRRWaves * kWave) void k_mg_rrestrict(RRArgs a, con
     const int buf = P & 1;
 #pragma unroll
     for (int u = 0; u < kRRPer; ++u) {
-      const d2a8 xv = S.xv[u];
+      const d2a8 xv = rr_tail(S.xv[u], xtail);
       // x window (2I - 2, 2I - 1, 2I, 2I + 1, 2I + 2)
       const double x0 = shr1(xv.x), x1 = shr1(xv.y), x4 = shl1(xv.x);
       const double s0 = shr1(sv[u].x), s1 = shr1(sv[u].y), s4 = shl1(sv[u].x);
@@ -1085,15 +1097,16 @@ void launch_mg_restrict(const MgXfer& x, const PcgState* st, const double* bf, c
 
 bool mg_restrict_folds_faces(const MgXfer& x) { return x.coarse[0] && x.fn[0] >= 3; }
 
-void launch_mg_rrestrict(const RRArgs& a, const PcgState* st, const double* b, const double* x, const FaceAdd& fa,
+bool launch_mg_rrestrict(const RRArgs& a, const PcgState* st, const double* b, const double* x, const FaceAdd& fa,
                          double* bc, const double* dinv_c, double omega_c, double* xc, hipStream_t s) {
   const int ncr = a.cn[a.raxis], ncq = a.cn[3 - a.raxis];
   const int nrb = (ncr + kRRWaves - 1) / kRRWaves;
-  if (a.qchunk > kRRQMax) return;  // (rr_setup keeps it below)
+  if (a.qchunk < 1 || a.qchunk > kRRQMax) return false;  // (rr_setup refuses such a chunk)
   const int nch = (ncq + a.qchunk - 1) / a.qchunk;
   const dim3 g((unsigned)((int64_t)a.nseg * nrb * nch)), bl(kRRWaves * kWave);
   if (a.raxis == 1) hipLaunchKernelGGL(k_mg_rrestrict<1>, g, bl, 0, s, a, st, b, x, fa, bc, dinv_c, omega_c, xc);
   else hipLaunchKernelGGL(k_mg_rrestrict<2>, g, bl, 0, s, a, st, b, x, fa, bc, dinv_c, omega_c, xc);
+  return true;
 }
 
 bool mg_prolong_blocks(const MgXfer& x) {

@@ -110,7 +110,7 @@ int mg_setup_dist(Ctx* c) {
   std::vector<double> tmp, Xf[3];
   for (int s = 0; s < 3; ++s) Xf[s] = storage_coords(c, s, tmp);
   const double da = c->P.dt * c->P.alpha;
-  HIPC(hipMalloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
+  HIPC(tv_dev_alloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
   HIPC(hipMemsetAsync(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
   c->mg_omega0 = mg_omega(mg_gershgorin(Xf, da));
   // the global hierarchy (the single-partition rule) and the plane owners of every level
@@ -344,12 +344,12 @@ int mg_setup_dist(Ctx* c) {
     const LevelRef r = level_ref(c, (size_t)(A - 1), nullptr);
     const int64_t nloc = (int64_t)r.g->n0 * r.g->n1 * r.g->n2;
     double** m = (A - 1 == 0) ? &c->mg_mask0 : &c->mg[A - 2].mask;
-    HIPC(hipMalloc(m, sizeof(double) * (size_t)std::max<int64_t>(1, nloc)));
+    HIPC(tv_dev_alloc(m, sizeof(double) * (size_t)std::max<int64_t>(1, nloc), kMemDoubles));
     launch_mg_ownmask(nloc, r.off, r.off + r.n_own, nullptr, *m, c->stream);
     HIPC(hipGetLastError());
   }
   if (c->mg_cgs) {  // s = A p of the single-reduction form
-    HIPC(hipMalloc(&c->mg_s, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
+    HIPC(tv_dev_alloc(&c->mg_s, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
     HIPC(hipMemsetAsync(c->mg_s, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
   }
   c->mg_on = true;
@@ -425,7 +425,7 @@ int mg_apply0_dist(Ctx* c, const double* T, const RedTail* tail) {
       launch_mg_restrict(C.xf, c->st, r.b, r.w, &fa0, mask, C.b, nullptr, 0.0, nullptr, s);
       if (int e = allreduce_vec(c, C.b, C.n)) return e;
       launch_mg_jacobi(C.n, c->st, C.b, nullptr, nullptr, C.dinv, C.omega, C.x, 0, s);  // pre-smoothing from 0
-      mg_level(c, A);  // the replicated V-cycle below (single-partition code; post-smooths level A)
+      if (int e = mg_level(c, A)) return e;  // the replicated V-cycle below (single-partition code; post-smooths level A)
     }
   }
   // ---- up: prolongation into the distributed levels, post-smoothing, ghosts

@@ -277,9 +277,13 @@ static int rr_setup(Ctx* c, MgLevel& L, const std::vector<double> (&Xp)[3], cons
   const char* te = std::getenv("TVFEM_RR_WG");
   const int target = te ? std::max(1, std::atoi(te)) : 256;
   const int64_t rowblocks = (x.cn[a.raxis] + 7) / 8;
-  a.qchunk = std::min(x.cn[qa], 64);  // <= kRRQMax (tv_mg.hip)
+  a.qchunk = std::min(x.cn[qa], kRRQMaxChunk);
   while ((int64_t)a.nseg * rowblocks * ((x.cn[qa] + a.qchunk - 1) / a.qchunk) < target && a.qchunk > 3)
     a.qchunk = (a.qchunk + 1) / 2;
+  // the launcher refuses any other chunk (the kernel's weight stage holds kRRQMaxChunk planes)
+  if (a.qchunk < 1 || a.qchunk > kRRQMaxChunk)
+    return c->fail(TV_ERR_STATE, "GMG: fused residual restriction: march chunk " + std::to_string(a.qchunk) +
+                                     " outside [1, " + std::to_string(kRRQMaxChunk) + "]");
   a.on = 1;
   return TV_OK;
 }
@@ -305,7 +309,7 @@ int mg_level_vectors(Ctx* c, MgLevel& L) {
   L.n = (int64_t)L.g.n0 * L.g.n1 * L.g.n2;
   for (double** q : {&L.T, &L.b, &L.x, &L.w, &L.dinv}) {
     void* p = nullptr;
-    HIPC(hipMalloc(&p, sizeof(double) * (size_t)std::max<int64_t>(1, L.n)));
+    HIPC(tv_dev_alloc(&p, sizeof(double) * (size_t)std::max<int64_t>(1, L.n), kMemDoubles));
     HIPC(hipMemsetAsync(p, 0, sizeof(double) * (size_t)std::max<int64_t>(1, L.n), c->stream));
     L.bufs.push_back(p);
     *q = static_cast<double*>(p);
@@ -329,12 +333,12 @@ int mg_setup(Ctx* c) {
   std::vector<double> tmp, Xf[3];
   for (int s = 0; s < 3; ++s) Xf[s] = storage_coords(c, s, tmp);
   const double da = c->P.dt * c->P.alpha;
-  HIPC(hipMalloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
+  HIPC(tv_dev_alloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
   HIPC(hipMemsetAsync(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
   if (dg) {
     // level 1: the CG1 space of the same box (two-level DG -> CG, then the CG hierarchy)
     c->mg_dg = true;
-    HIPC(hipMalloc(&c->dggface, sizeof(double) * (size_t)dg_gface_size(c->dg)));
+    HIPC(tv_dev_alloc(&c->dggface, sizeof(double) * (size_t)dg_gface_size(c->dg), kMemDoubles));
     c->mg_omega0 = 0.0;  // estimated at the first solve, at its T (mg_dg_weight)
     if (int e = mg_add_cg_level(c, Xf, da)) return e;
   } else {
@@ -469,7 +473,9 @@ void mg_prolong_from(Ctx* c, size_t ci, double* xf, const double* mask) {
   }
 }
 
-void mg_level(Ctx* c, size_t l) {
+static const char kRRChunkMsg[] = "GMG: fused residual restriction refused (march chunk out of range)";
+
+int mg_level(Ctx* c, size_t l) {
   MgLevel& L = c->mg[l - 1];
   hipStream_t s = c->stream;
   if (l < c->mg.size()) {
@@ -477,7 +483,8 @@ void mg_level(Ctx* c, size_t l) {
     const FaceAdd fa = cg_face_add(L.g, 0);
     if (C.rr.on && fa.on) {  // fused residual restriction (no J x of this level)
       launch_cg_facet_faces(L.g, L.T, L.x, c->st, s);
-      launch_mg_rrestrict(C.rr, c->st, L.b, L.x, cg_face_add_all(L.g), C.b, C.dinv, C.omega, C.x, s);
+      if (!launch_mg_rrestrict(C.rr, c->st, L.b, L.x, cg_face_add_all(L.g), C.b, C.dinv, C.omega, C.x, s))
+        return c->fail(TV_ERR_STATE, kRRChunkMsg);
     } else if (fa.on && mg_restrict_folds_faces(C.xf)) {  // the restriction adds the facet terms (no k_cg_addfaces)
       launch_cg_japply_partial(L.g, L.T, L.x, L.w, c->st, s);
       launch_mg_restrict(C.xf, c->st, L.b, L.w, &fa, nullptr, C.b, C.dinv, C.omega, C.x, s);
@@ -485,13 +492,14 @@ void mg_level(Ctx* c, size_t l) {
       launch_cg_japply(L.g, L.T, L.x, L.w, nullptr, nullptr, s, c->st);
       launch_mg_restrict(C.xf, c->st, L.b, L.w, nullptr, nullptr, C.b, C.dinv, C.omega, C.x, s);
     }
-    mg_level(c, l + 1);
+    if (int e = mg_level(c, l + 1)) return e;
     mg_prolong_from(c, l, L.x, nullptr);
     launch_cg_japply_partial(L.g, L.T, L.x, L.w, c->st, s);
     // post-smoothing, unless the prolongation out of this level applies it (mg_prolong_from)
     if (!mg_prolong_smooths(L.xf))
       launch_mg_jacobi(L.n, c->st, L.b, L.w, &fa, L.dinv, L.omega, L.x, 1, s);
   }
+  return TV_OK;
 }
 
 // level 0: x0 = omega dinv r is in c->mgx (k_mg_update); coarse correction,
@@ -513,12 +521,12 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
       launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, nullptr, 0.0, nullptr, kg0, s);
       if (int e = allreduce_vec(c, C.b, C.n)) return -e;
       launch_mg_jacobi(C.n, c->st, C.b, nullptr, nullptr, C.dinv, C.omega, C.x, 0, s);  // pre-smoothing from 0
-      mg_level(c, 1);
+      if (int e = mg_level(c, 1)) return -e;
       launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, kg0, s);
     } else {
       launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
       launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, C.dinv, C.omega, C.x, 0, s);
-      mg_level(c, 1);
+      if (int e = mg_level(c, 1)) return -e;
       launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, 0, s);
     }
     launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
@@ -536,7 +544,8 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
       // b_1 = R (r - J x0) without J x0: the facet terms of x0 on every face,
       // then the fused residual restriction (RRArgs) with level 1's pre-smoothing
       launch_cg_facet_faces(c->cg, T, c->mgx, c->st, s);
-      launch_mg_rrestrict(C.rr, c->st, c->r, c->mgx, cg_face_add_all(c->cg), C.b, C.dinv, C.omega, C.x, s);
+      if (!launch_mg_rrestrict(C.rr, c->st, c->r, c->mgx, cg_face_add_all(c->cg), C.b, C.dinv, C.omega, C.x, s))
+        return -c->fail(TV_ERR_STATE, kRRChunkMsg);
     } else if (fa.on && mg_restrict_folds_faces(C.xf) && n < kMgFoldFacesNodes) {
       launch_cg_japply_partial(c->cg, T, c->mgx, c->w, c->st, s);
       launch_mg_restrict(C.xf, c->st, c->r, c->w, &fa, mask, C.b, C.dinv, C.omega, C.x, s);
@@ -544,7 +553,7 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
       launch_cg_japply(c->cg, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
       launch_mg_restrict(C.xf, c->st, c->r, c->w, nullptr, mask, C.b, C.dinv, C.omega, C.x, s);
     }
-    mg_level(c, 1);
+    if (int e = mg_level(c, 1)) return -e;
     mg_prolong_from(c, 0, c->mgx, mask);
   }
   // J x, post-smoothing and (z.z, z.r) in the march epilogue (+ the side-face pass)
@@ -573,8 +582,8 @@ int mg_iteration(Ctx* c, const double* T, int it) {
     launch_mg_update(n, c->st, c->pA, c->pB, c->w, &fa, c->dinv, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it, 0,
                      c->stream);
   RedTail t2{c->counters + kTailCounters, c->partials, c->sums, c->st, 3, nullptr};
-  mg_apply0(c, T, &t2);  // z <- V(r); z.z, z.r; beta, convergence
-  return TV_OK;
+  const int nrec = mg_apply0(c, T, &t2);  // z <- V(r); z.z, z.r; beta, convergence
+  return nrec < 0 ? -nrec : TV_OK;
 }
 
 int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
@@ -593,7 +602,7 @@ int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
     launch_mg_update(n, c->st, c->pA, c->pB, c->w, nullptr, c->dinv, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0, 1,
                      c->stream);  // dx <- 0, x0 <- omega dinv r
   RedTail t0{c->counters + kTailCounters, c->partials, c->sums, c->st, 1, nullptr};
-  mg_apply0(c, T, &t0);  // z <- V(r); dp, beta (KSPCG init)
+  if (const int nrec = mg_apply0(c, T, &t0); nrec < 0) return -nrec;  // z <- V(r); dp, beta (KSPCG init)
   if (c->ktime && c->ts_next + c->O.ksp_max_it + 8 > kTsCap)
     if (int e = ts_flush(c)) return e;
   // an MG iteration is ~25 launches: the previous solve's count (hint) is queued
@@ -719,7 +728,7 @@ int tv_precond_apply(void* ctx, const double* r_dev, double* z_dev) {
       launch_dg_bsmooth(c->dg, c->st, c->r, nullptr, c->dggface, c->mg_omega0, c->mgx, 0, s);
     else
       launch_mg_jacobi(n, c->st, c->r, nullptr, nullptr, c->dinv, c->mg_omega0, c->mgx, 0, s);
-    mg_apply0(c, T, nullptr);
+    if (const int nrec = mg_apply0(c, T, nullptr); nrec < 0) return -nrec;
     HIPC(hipMemcpyAsync(z_dev, c->z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
   }
   HIPC(hipGetLastError());

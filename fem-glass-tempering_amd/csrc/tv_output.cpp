@@ -393,7 +393,7 @@ bool output_add_field(Output* o, const std::string& name, int ncomp, bool dg, si
 bool output_start(Output* o, int device, std::string& err) {
   o->device = device;
   for (int k = 0; k < 2; ++k) {
-    if (hipMalloc(&o->dstage[k], sizeof(double) * std::max<size_t>(1, o->set_n)) != hipSuccess ||
+    if (tv_dev_alloc(&o->dstage[k], sizeof(double) * std::max<size_t>(1, o->set_n), kMemDoubles) != hipSuccess ||
         hipHostMalloc(&o->hstage[k], sizeof(double) * std::max<size_t>(1, o->set_n)) != hipSuccess ||
         hipEventCreateWithFlags(&o->ready[k], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&o->copied[k], hipEventDisableTiming) != hipSuccess) {
@@ -461,7 +461,7 @@ std::string output_destroy(Output* o) {
   if (o->th.joinable()) o->th.join();
   std::string e = o->err;
   for (int k = 0; k < 2; ++k) {
-    if (o->dstage[k]) hipFree(o->dstage[k]);
+    if (o->dstage[k]) tv_dev_free(o->dstage[k]);
     if (o->hstage[k]) hipHostFree(o->hstage[k]);
     if (o->ready[k]) hipEventDestroy(o->ready[k]);
     if (o->copied[k]) hipEventDestroy(o->copied[k]);

@@ -960,7 +960,7 @@ static bool structured_topology(int dim, int64_t nv, int64_t nc, const int64_t* 
 template <class T>
 static int um_upload(UmDevice* d, const std::vector<T>& h, T** out, std::string& err) {
   void* p = nullptr;
-  UMC(hipMalloc(&p, sizeof(T) * std::max<size_t>(1, h.size())));
+  UMC(tv_dev_alloc(&p, sizeof(T) * std::max<size_t>(1, h.size()), mem_kind<T>()));
   d->bufs.push_back(p);
   if (!h.empty()) UMC(hipMemcpy(p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
   *out = static_cast<T*>(p);
@@ -970,7 +970,7 @@ static int um_upload(UmDevice* d, const std::vector<T>& h, T** out, std::string&
 template <class T>
 static int um_alloc(UmDevice* d, size_t n, T** out, std::string& err) {
   void* p = nullptr;
-  UMC(hipMalloc(&p, sizeof(T) * std::max<size_t>(1, n)));
+  UMC(tv_dev_alloc(&p, sizeof(T) * std::max<size_t>(1, n), mem_kind<T>()));
   d->bufs.push_back(p);
   *out = static_cast<T*>(p);
   return 0;
@@ -979,7 +979,7 @@ static int um_alloc(UmDevice* d, size_t n, T** out, std::string& err) {
 static void release(UmDevice* d, void* p) {
   auto it = std::find(d->bufs.begin(), d->bufs.end(), p);
   if (it != d->bufs.end()) {
-    hipFree(p);
+    tv_dev_free(p);
     d->bufs.erase(it);
   }
 }
@@ -1043,7 +1043,7 @@ static int n_threads() {
 
 void um_free(UmDevice* d) {
   if (!d) return;
-  for (void* p : d->bufs) hipFree(p);
+  for (void* p : d->bufs) tv_dev_free(p);
   delete d;
 }
 

@@ -44,6 +44,7 @@ EXPORTS = [
     "tv_ensemble_create", "tv_ensemble_destroy", "tv_ensemble_set_initial_condition", "tv_ensemble_step",
     "tv_ensemble_get_field", "tv_ensemble_set_field", "tv_ensemble_stats",
     "tv_ensemble_set_schedule", "tv_ensemble_history_open", "tv_ensemble_history_read",
+    "tv_guard_check",
 ]
 
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
@@ -200,6 +201,7 @@ def load_library():
         "tv_ensemble_set_schedule": (C.c_int, [vp, C.POINTER(EnsembleSchedule)]),
         "tv_ensemble_history_open": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int]),
         "tv_ensemble_history_read": (C.c_int, [vp, dp, C.c_size_t, ip]),
+        "tv_guard_check": (C.c_int, [i64p, i64p, i64p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

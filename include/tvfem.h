@@ -291,6 +291,17 @@ int tv_abi_version(void);
 const char* tv_last_error(const void* ctx);      /* NULL ctx: global error   */
 void tv_default_options(tv_options* opts);
 void tv_default_params(tv_params* p);            /* main.py:29-55 + tableaux */
+/* Red-zone test mode of the library's device memory.  With the environment
+ * variable TVFEM_ALLOC_GUARD=<KiB> set while contexts are created, every device
+ * allocation of the library lies between two guards of at least that size,
+ * filled with NaN bit patterns (arrays of doubles) or zeros (anything else).
+ * This call waits for the device and compares every live guard with its fill:
+ * n_guarded = live guarded allocations, n_damaged = those with a changed guard
+ * byte (tv_last_error(NULL) then names the first one's size and the damaged
+ * offset relative to its data), guard_bytes = the smallest guard in force.
+ * With no guarded allocation live: zeros, and no GPU call is made.  TV_ERR_ARG
+ * for a null pointer. */
+int tv_guard_check(int64_t* n_guarded, int64_t* n_damaged, int64_t* guard_bytes);
 
 int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params* params,
               const tv_options* opts, int device, void** ctx_out);
@@ -363,7 +374,10 @@ int tv_set_ksp_tolerances(void* ctx, double rtol, double atol, double dtol, int 
 /* ---- operators (device pointers, owned T-dofs, length n_owned) ----------
  * The context stream is non-blocking: these calls first wait for all work
  * already queued on the device (hipDeviceSynchronize), so inputs written on
- * another stream (e.g. torch's) before the call are complete when it reads them. */
+ * another stream (e.g. torch's) before the call are complete when it reads them.
+ * T_dev, F_dev, x_dev, y_dev, d_dev, r_dev and z_dev need to be 8-byte aligned
+ * (a double's own alignment), no more: the kernels address them by elements,
+ * and nothing outside [p, p + n_owned) is read or written. */
 int tv_residual(void* ctx, const double* T_dev, double* F_dev);     /* F(T; T_prev) */
 int tv_jacobian_apply(void* ctx, const double* x_dev, double* y_dev); /* J(T)·x      */
 int tv_jacobian_diag(void* ctx, double* d_dev);                       /* diag J(T)   */
