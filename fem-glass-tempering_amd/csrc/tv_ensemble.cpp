@@ -1,7 +1,8 @@
-// Ensembles of independent 1D CG1 bars (parameter studies of the reference's
-// own main.py workload): host side of csrc/tv_ensemble.hip.  C-ABI:
-// include/tvfem.h, tv_ensemble_*.
-//   tv_ensemble_create                 ThermoViscoProblem.__init__ once per bar
+// Ensembles of independent 1D bars (parameter studies of the reference's own
+// main.py workload): host side of csrc/tv_ensemble.hip (CG1 temperature and
+// stress) and csrc/tv_ensemble_dg.hip (DG1 temperature, CG1 stress: main.py's
+// own fe_config).  C-ABI: include/tvfem.h, tv_ensemble_*.
+//   tv_ensemble_create / _create_dg    ThermoViscoProblem.__init__ once per bar
 //   tv_ensemble_set_initial_condition  _set_initial_condition (:187-233), each bar's T_0
 //   tv_ensemble_step                   n_steps x solve_timestep (:367-381) minus the
 //                                      file output, every bar, one launch per
@@ -18,6 +19,10 @@ namespace tv {
 // memory latency, the same from 64 to 16384 bars), so one launch stays below
 // half a second, far from any watchdog, while a 500-step main.py run of a
 // bar of up to 262 nodes is still a single launch.
+// A DG handle counts its T dofs (two per cell) in place of the nodes: measured
+// 2.2 us per T dof and step on the 48-cell main.py bar from 64 to 1024 bars
+// (one division per cell, six scratch values per cell), 2.8 at 4096 and 3.2 at
+// 16384 bars, so a launch stays below 0.42 s.
 constexpr int64_t kMaxNodeStepsPerLaunch = 1 << 17;
 
 struct Ens {
@@ -38,6 +43,9 @@ struct Ens {
   bool ext() const { return x.n_stages > 0 || x.n_probes > 0; }
   double* field[TV_NUM_FIELDS] = {};
   int bs[TV_NUM_FIELDS] = {};
+  int nd[TV_NUM_FIELDS] = {};  // dofs per bar of the field's family
+  bool dg = false;             // DG1 temperature (tv_ensemble_create_dg): nT = 2 n_cells, nS = n_cells + 1
+  int nT = 0, nS = 0;          // T-family / sigma-family dofs per bar (CG: both n_cells + 1)
   int steps_done = 0;
   int fail(int code, const std::string& m) {
     err = m;
@@ -63,19 +71,20 @@ int ens_alloc(Ens* c, size_t bytes, void** out, int kind = kMemDoubles) {
   return TV_OK;
 }
 
-int ens_alloc_field(Ens* c, int id, int bs) {
+int ens_alloc_field(Ens* c, int id, int bs, int n_dofs) {
   void* p = nullptr;
-  if (int e = ens_alloc(c, sizeof(double) * (size_t)bs * c->a.n_nodes * c->a.nb_pad, &p)) return e;
+  if (int e = ens_alloc(c, sizeof(double) * (size_t)bs * n_dofs * c->a.nb_pad, &p)) return e;
   c->field[id] = static_cast<double*>(p);
   c->bs[id] = bs;
+  c->nd[id] = n_dofs;
   return TV_OK;
 }
 
-// host [bar][node * bs + comp]  <->  device [comp][node][bar]
+// host [bar][dof * bs + comp]  <->  device [comp][dof][bar], dof counted in the field's own family
 int ens_transfer(Ens* c, int field, double* host, size_t n_values, bool to_device) {
   if (field < 0 || field >= TV_NUM_FIELDS || !c->field[field])
     return c->fail(TV_ERR_STATE, "tv_ensemble: field " + std::to_string(field) + " is not part of an ensemble's state");
-  const int bs = c->bs[field], n = c->a.n_nodes, nb = c->a.n_bars;
+  const int bs = c->bs[field], n = c->nd[field], nb = c->a.n_bars;
   const int64_t pad = c->a.nb_pad;
   if (!host || n_values != (size_t)nb * n * bs) return c->fail(TV_ERR_ARG, "tv_ensemble: field size mismatch");
   std::vector<double> dev((size_t)bs * n * pad);
@@ -110,30 +119,32 @@ int ens_push_ext(Ens* c) {
   return TV_OK;
 }
 
-}  // namespace
-}  // namespace tv
-
-using namespace tv;
-
-extern "C" {
-
-int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P, const tv_options* opts,
-                       int device, void** ens_out) {
+// tv_ensemble_create (dg = false) and tv_ensemble_create_dg (dg = true): every refusal but the device's
+// is decided before the first HIP call
+int ens_create(const char* fn, bool dg, const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P,
+               const tv_options* opts, int device, void** ens_out) {
   if (!d || !fe || !P || !ens_out) {
-    set_global_error("tv_ensemble_create: null argument");
+    set_global_error(std::string(fn) + ": null argument");
     return TV_ERR_ARG;
   }
   *ens_out = nullptr;
-  auto bad = [](const std::string& m) {
-    set_global_error("tv_ensemble_create: " + m);
+  auto bad = [fn](const std::string& m) {
+    set_global_error(std::string(fn) + ": " + m);
     return TV_ERR_ARG;
   };
   if (d->n_bars < 1) return bad("n_bars must be at least 1");
   if (d->n_cells < 1) return bad("n_cells must be at least 1");
   if (!d->coords) return bad("coords is null");
-  if (fe->T_family != TV_CG || fe->sigma_family != TV_CG || fe->T_degree != 1 || fe->sigma_degree != 1)
+  const bool cg_stress = fe->sigma_family == TV_CG && fe->sigma_degree == 1;
+  if (!dg && (fe->T_family != TV_CG || fe->T_degree != 1 || !cg_stress))
     return bad("only CG1 temperature with CG1 stress is implemented (DG temperature is out of scope)");
+  if (dg && (fe->T_family != TV_DG || fe->T_degree != 1 || !cg_stress)) {
+    if (fe->T_family == TV_CG && fe->T_degree == 1 && cg_stress)
+      return bad("only DG1 temperature with CG1 stress is implemented here (CG1 temperature: tv_ensemble_create)");
+    return bad("only DG1 temperature with CG1 stress is implemented");
+  }
   auto c = std::make_unique<Ens>();
+  c->dg = dg;
   if (opts) c->O = *opts;
   else tv_default_options(&c->O);
   if (c->O.model_mode != TV_MODEL_REFERENCE) return bad("model_mode PAPER is not implemented for ensembles");
@@ -146,8 +157,9 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
     for (int i = 0; i + 1 < n; ++i)
       if (!(X[i + 1] > X[i])) return bad("coordinates of bar " + std::to_string(b) + " are not strictly increasing");
   }
+  const int nT = dg ? 2 * (n - 1) : n, nS = n;  // dofs per bar of the T family / the sigma family
   const int64_t pad = ((int64_t)nb + kWave - 1) / kWave * kWave;
-  if (pad * n * 6 > INT64_C(1) << 40 || pad > INT32_MAX) return bad("ensemble too large");
+  if (pad * nT * 6 > INT64_C(1) << 40 || pad > INT32_MAX) return bad("ensemble too large");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
     set_global_error("no HIP device available: libtvfem requires an MI355X (gfx950) GPU");
@@ -164,6 +176,8 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   a.n_bars = nb;
   a.nb_pad = (int)pad;
   a.n_nodes = n;
+  c->nT = nT;
+  c->nS = nS;
   a.max_it = c->O.newton_max_it;
   a.rtol = c->O.newton_rtol;
   a.atol = c->O.newton_atol;
@@ -189,13 +203,16 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   }
   int rc = TV_OK;
   void *dpar = nullptr, *dcell = nullptr, *scr = nullptr, *its = nullptr, *fs = nullptr, *tot = nullptr;
-  static const int kState[][2] = {{TV_F_T, 1}, {TV_F_T_PREV, 1}, {TV_F_TF, 1}, {TV_F_TF_PARTIAL, 6}, {TV_F_PHI, 1},
-                                  {TV_F_XI, 1}, {TV_F_SIGMA, 1}, {TV_F_S_TILDE, 6}, {TV_F_SIGMA_TILDE, 6}};
+  // id, block size, family (0: T, 1: sigma)
+  static const int kState[][3] = {{TV_F_T, 1, 0}, {TV_F_T_PREV, 1, 0}, {TV_F_TF, 1, 0}, {TV_F_TF_PARTIAL, 6, 0},
+                                  {TV_F_PHI, 1, 0}, {TV_F_XI, 1, 0}, {TV_F_SIGMA, 1, 1}, {TV_F_S_TILDE, 6, 1},
+                                  {TV_F_SIGMA_TILDE, 6, 1}};
   for (const auto& s : kState)
-    if (rc == TV_OK) rc = ens_alloc_field(c.get(), s[0], s[1]);
+    if (rc == TV_OK) rc = ens_alloc_field(c.get(), s[0], s[1], s[2] ? nS : nT);
   if (rc == TV_OK) rc = ens_alloc(c.get(), par.size() * sizeof(double), &dpar);
   if (rc == TV_OK) rc = ens_alloc(c.get(), cell.size() * sizeof(double), &dcell);
-  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(double) * 2 * n * pad, &scr);
+  // Thomas scratch [2][n_nodes][pad]; DG: C and d of the block elimination, [6][n_cells][pad]
+  if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(double) * (dg ? (size_t)6 * (n - 1) : (size_t)2 * n) * pad, &scr);
   if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &its, kMemOther);
   if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int) * pad, &fs, kMemOther);
   if (rc == TV_OK) rc = ens_alloc(c.get(), sizeof(int64_t) * pad, &tot, kMemOther);
@@ -246,7 +263,8 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   }
   ViscoFields& v = c->vf;
   std::memset(&v, 0, sizeof(v));
-  v.sT = v.sS = (int64_t)n * pad;
+  v.sT = (int64_t)nT * pad;
+  v.sS = (int64_t)nS * pad;
   v.T = c->field[TV_F_T]; v.Tp = c->field[TV_F_T_PREV];
   v.phi = c->field[TV_F_PHI]; v.xi = c->field[TV_F_XI];
   v.Tf = c->field[TV_F_TF]; v.Tfp = c->field[TV_F_TF_PARTIAL];
@@ -258,6 +276,24 @@ int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const 
   }
   *ens_out = c.release();
   return TV_OK;
+}
+
+}  // namespace
+}  // namespace tv
+
+using namespace tv;
+
+extern "C" {
+
+int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P, const tv_options* opts,
+                       int device, void** ens_out) {
+  return ens_create("tv_ensemble_create", false, d, fe, P, opts, device, ens_out);
+}
+
+
+int tv_ensemble_create_dg(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P,
+                          const tv_options* opts, int device, void** ens_out) {
+  return ens_create("tv_ensemble_create_dg", true, d, fe, P, opts, device, ens_out);
 }
 
 
@@ -284,7 +320,7 @@ int tv_ensemble_set_initial_condition(void* ens) {
   if (!c) return TV_ERR_ARG;
   hipSetDevice(c->device);
   // __set_IC_T, __set_IC_Tf, __set_IC_Tf_partial (ThermoViscoProblem.py:193-233) with each bar's T_0
-  const int n = c->a.n_nodes;
+  const int n = c->nT;  // all four are T-family fields
   const int64_t pad = c->a.nb_pad;
   std::vector<double> v((size_t)6 * n * pad, 0.0);
   for (int q = 0; q < 6 * n; ++q)
@@ -310,13 +346,13 @@ int tv_ensemble_step(void* ens, int n_steps, int thermal_only) {
                                      " x every " + std::to_string(c->x.every) + "); no bar has advanced");
   hipSetDevice(c->device);
   const int before = c->steps_done;
-  const int per_launch = (int)std::max<int64_t>(1, kMaxNodeStepsPerLaunch / c->a.n_nodes);
+  const int per_launch = (int)std::max<int64_t>(1, kMaxNodeStepsPerLaunch / c->nT);
   for (int left = n_steps; left > 0;) {
     EnsArgs a = c->a;
     a.n_steps = std::min(left, per_launch);
     a.step_base = c->steps_done;
     a.thermal_only = thermal_only ? 1 : 0;
-    launch_ensemble(a, c->vc, c->vf, c->ext() ? c->dx : nullptr, c->stream);
+    (c->dg ? launch_ensemble_dg : launch_ensemble)(a, c->vc, c->vf, c->ext() ? c->dx : nullptr, c->stream);
     HIPC(hipGetLastError());
     c->steps_done += a.n_steps;
     left -= a.n_steps;

@@ -462,6 +462,11 @@ struct EnsExt {
 };
 // x: device pointer, or nullptr for the plain kernel
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);
+// DG1 temperature with CG1 stress (tv_ensemble_dg.hip): the same arguments read as n_nodes mesh nodes =
+// sigma dofs and 2 (n_nodes - 1) T dofs (2 c + l) per bar, T / Tp [2 (n_nodes - 1)][nb_pad], scr
+// [6][n_nodes - 1][nb_pad] (C and d of the block elimination), ViscoFields with sT = 2 (n_nodes - 1) nb_pad
+// and sS = n_nodes nb_pad; EnsExt::probes stay mesh nodes
+void launch_ensemble_dg(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);
 
 // PCG vector kernels over the owned range [0, n) of already-offset pointers
 constexpr int kVecBlocks = 1024;        // grid cap of the vector kernels

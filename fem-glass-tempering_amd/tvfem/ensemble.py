@@ -5,13 +5,20 @@ A parameter study of the reference's own workload (main.py: one
 through-thickness bar): every bar has the same cell count and may have its
 own node coordinates (thickness, grading) and its own ``htc``, ``T_0``,
 ``T_ambient``, ``epsilon``, ``alpha`` and ``f``; ``dt`` and every other model
-parameter are shared.  CG1 temperature and stress, reference model mode.
+parameter are shared.  Reference model mode; ``config`` is CG1 temperature with
+CG1 stress, or DG1 temperature with CG1 stress (main.py's own ``fe_config``: SIPG
+on the interior nodes, two T dofs per cell numbered ``2 c + l``).  With DG
+temperature the T-family fields (T, T_prev, Tf, Tf_partial, phi, xi) have
+``n_dofs_T = 2 n_cells`` dofs per bar and the stress fields ``n_dofs_sigma =
+n_cells + 1``; history probes stay mesh nodes, T and Tf being recorded at the
+node's source dof (``2 i``, and ``2 n_cells - 1`` for the last node) and sigma at
+the node.
 
     ens = ThermoViscoEnsemble(mesh, (0.0, 50.0), 0.1, fe_config,
                               dict(model_params, htc=np.linspace(50, 1000, 4096)))
     ens.setup()
     ens.solve()
-    sigma = ens.get_field("sigma")        # (n_bars, n_dofs)
+    sigma = ens.get_field("sigma")        # (n_bars, n_dofs_sigma)
 
 A process schedule lets ``htc``, ``T_ambient`` and ``epsilon`` of each bar change
 at times of its own (a quench of per-bar length, then after-cooling), and a
@@ -45,6 +52,8 @@ PER_BAR_KEYS = ("htc", "T_0", "T_ambient", "epsilon", "alpha", "f")
 # the state an ensemble keeps (names as ThermoViscoProblem.get_field) and its block size per dof
 STATE_FIELDS = {"T": 1, "T_prev": 1, "Tf": 1, "Tf_partial": 6, "phi": 1, "xi": 1, "sigma": 1,
                 "s_tilde_partial": 6, "sigma_tilde_partial": 6}
+# the fields that live on the stress space (every other state field lives on the temperature space)
+SIGMA_FAMILY = ("sigma", "s_tilde_partial", "sigma_tilde_partial")
 _FAMILIES = {"CG": N.TV_CG, "DG": N.TV_DG}
 # what a schedule stage may change, and how it says where it ends
 STAGE_KEYS = ("htc", "T_ambient", "epsilon")
@@ -120,8 +129,14 @@ class ThermoViscoEnsemble:
         self.time = time
         self.t = self.time[0]
         self.n_steps = ceil((self.time[1] - self.time[0]) / self.dt)
-        self.n_dofs = self.n_cells + 1
         self.config = config
+        # DG1 temperature with CG1 stress has its own kernel and constructor; every other pairing goes to
+        # tv_ensemble_create, which accepts CG1 / CG1 and refuses the rest
+        self._dg = (config["T"]["element"] == "DG" and int(config["T"]["degree"]) == 1
+                    and config["sigma"]["element"] == "CG" and int(config["sigma"]["degree"]) == 1)
+        self.n_dofs_T = 2 * self.n_cells if self._dg else self.n_cells + 1
+        self.n_dofs_sigma = self.n_cells + 1
+        self.n_dofs = self.n_dofs_T
         self.coords = np.ascontiguousarray(np.stack([m.axes[0] for m in mlist]))
         self._arrays = arrays
         # ---- process schedule and probe history: everything is decided before anything is created
@@ -151,8 +166,8 @@ class ThermoViscoEnsemble:
             opts.newton_max_it = newton_max_it
         opts.error_on_nonconvergence = 1 if error_on_nonconvergence else 0
         ens = C.c_void_p()
-        N.check(lib.tv_ensemble_create(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), device,
-                                       C.byref(ens)))
+        create = lib.tv_ensemble_create_dg if self._dg else lib.tv_ensemble_create
+        N.check(create(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), device, C.byref(ens)))
         self._ens = ens
         try:
             if self._schedule is not None:
@@ -250,8 +265,10 @@ class ThermoViscoEnsemble:
 
     # ---- state ---------------------------------------------------------------------------
     def get_field(self, name: str) -> np.ndarray:
-        """(n_bars, n_dofs * bs) array, per bar the reference's interleaved layout."""
-        out = np.empty((self.n_bars, self.n_dofs * STATE_FIELDS.get(name, 1)))
+        """(n_bars, dofs * bs) array, per bar the reference's interleaved layout; dofs is
+        ``n_dofs_sigma`` for the stress fields and ``n_dofs_T`` for the others."""
+        dofs = self.n_dofs_sigma if name in SIGMA_FAMILY else self.n_dofs_T
+        out = np.empty((self.n_bars, dofs * STATE_FIELDS.get(name, 1)))
         N.check(self._lib.tv_ensemble_get_field(self._ens, N.FIELD_ID[name],
                                                 out.ctypes.data_as(C.POINTER(C.c_double)), out.size), self._ens)
         return out

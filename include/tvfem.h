@@ -60,7 +60,8 @@ extern "C" {
                                tv_last_converged;
                             8: tv_options lost the unused use_graphs field;
                                (still 8, additions only: tv_ensemble_desc and the tv_ensemble_* functions;
-                               then tv_ensemble_schedule, tv_ensemble_set_schedule, tv_ensemble_history_*) */
+                               then tv_ensemble_schedule, tv_ensemble_set_schedule, tv_ensemble_history_*;
+                               then tv_ensemble_create_dg) */
 
 /* status codes */
 #define TV_OK 0
@@ -426,6 +427,22 @@ typedef struct {
 
 int tv_ensemble_create(const tv_ensemble_desc* desc, const tv_fe_config* fe, const tv_params* shared,
                        const tv_options* opts, int device, void** ens_out);
+/* The same bars with DG1 temperature and CG1 stress, main.py's own fe_config
+ * (csrc/tv_ensemble_dg.hip: SIPG interior-facet terms, '+' = the lower cell,
+ * the block-tridiagonal Newton systems solved directly).  Accepts exactly
+ * T = DG1, sigma = CG1; every other pairing returns TV_ERR_ARG, like the other
+ * refusals of tv_ensemble_create before the GPU is touched.  Every other
+ * tv_ensemble_* function takes the handle.  State of a DG handle, per bar:
+ *   T family      T, T_PREV, TF, TF_PARTIAL, PHI, XI    nT = 2 n_cells dofs,
+ *                 dof 2 c + l = local vertex l of cell c
+ *   sigma family  SIGMA, S_TILDE, SIGMA_TILDE            nS = n_cells + 1 dofs,
+ *                 the mesh nodes
+ * get_field / set_field check n_values against the field's own count.  A
+ * history probe stays a mesh node i in [0, n_cells]: sigma is recorded at the
+ * node, T and Tf at its source dof src(i) = 2 i for i < n_cells and
+ * src(n_cells) = 2 n_cells - 1 (the last cell in cell order wins). */
+int tv_ensemble_create_dg(const tv_ensemble_desc* desc, const tv_fe_config* fe, const tv_params* shared,
+                          const tv_options* opts, int device, void** ens_out);
 int tv_ensemble_destroy(void* ens);
 /* T = T_prev = Tf = Tf_partial = each bar's own T_0 (as tv_set_initial_condition;
  * the other fields and the Newton / failure records keep their values) */

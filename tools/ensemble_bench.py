@@ -38,6 +38,24 @@ of the unscheduled run there, measured by the parent's own copy of this tool
 in a child process of the same session (numbers of different machines or days
 are not comparable).  The margin the two new figures are held against is
 the larger of 2 % and three times the parent's own rep-to-rep spread.
+
+--dg measures the DG1-temperature / CG1-stress ensemble (main.py's own
+fe_config, csrc/tv_ensemble_dg.hip; default output
+profiles/ensemble_dg_bench.json): the same bar (48 cells, 96 T dofs), parameters
+and sizes, against --seq-bars bars one after another through ThermoViscoProblem
+with the same DG / CG config, and in the same run the CG1 / CG1 ensemble, for
+the DG / CG time ratio beside the ratio of the algorithmic bytes:
+
+  per cell and Newton iteration  176 B  forward sweep reads 2 T, 2 T_prev and
+                                        two cell coefficients, writes the six
+                                        values of C and d; back substitution
+                                        reads them and 2 T, writes 2 T
+  per T dof and step             144 B  t_part: reads T, T_prev, 6 Tf_partial;
+                                        writes 6 Tf_partial, Tf, phi, xi, T_prev
+  per mesh node and step         200 B  s_part: reads 12 tilde values; writes
+                                        them and sigma
+
+The same 64x floor at 4096 bars holds; the tool exits non-zero below it.
 """
 import argparse
 import json
@@ -61,6 +79,19 @@ BYTES_NODE_NEWTON = 80
 BYTES_NODE_STEP = 344
 FLOOR = 64.0
 CFG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
+CFG_DG = {"T": {"element": "DG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
+DG_BYTES_CELL_NEWTON = 176
+DG_BYTES_TDOF_STEP = 144
+DG_BYTES_NODE_STEP = 200
+# the cross-compiler's resource report of csrc/tv_ensemble_dg.hip (gfx950, -O3 -ffp-contract=off); DESIGN.md
+# section 15, "DG temperature"
+DG_KERNEL_RECORD = {
+    "plain_instantiation": {"vgpr_count": 236, "sgpr_spill_count": 62, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0, "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 240, "sgpr_spill_count": 61, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 52, "scratch_instructions": 0,
+                                "occupancy_waves_per_simd": 2},
+}
 # the cross-compiler's resource report of csrc/tv_ensemble.hip (gfx950, -O3 -ffp-contract=off), recorded with
 # the change that added schedules; DESIGN.md section 15 says how it was obtained
 KERNEL_RECORD = {
@@ -178,6 +209,84 @@ def scheduled_bench(args):
     print(json.dumps({"out": out}))
 
 
+def dg_bench(args):
+    from geometry import graded_bar
+    from main import model_params
+    from tvfem import ThermoViscoEnsemble
+    from tvfem.problem import ThermoViscoProblem
+
+    mesh = graded_bar()
+    n_nodes = mesh.num_vertices
+    n_cells = n_nodes - 1
+    span = (0.0, args.steps * 0.1)
+
+    def make(cfg):
+        def ensemble(n_bars):
+            ens = ThermoViscoEnsemble(mesh, span, 0.1, cfg, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)))
+            ens.setup()
+            return ens
+        return ensemble
+
+    dg = _time_ensembles(make(CFG_DG), args.sizes, args.steps, args.reps)
+    cg = _time_ensembles(make(CFG), args.sizes, args.steps, args.reps)
+    rows = []
+    for d, c in zip(dg, cg):
+        bar_steps = d["n_bars"] * args.steps
+        nbytes = bar_steps * (n_cells * DG_BYTES_CELL_NEWTON * d["newton_its_per_step"]
+                              + 2 * n_cells * DG_BYTES_TDOF_STEP + n_nodes * DG_BYTES_NODE_STEP)
+        cg_bytes = bar_steps * n_nodes * (BYTES_NODE_NEWTON * c["newton_its_per_step"] + BYTES_NODE_STEP)
+        row = dict(d, bar_steps_per_s=bar_steps / d["wall_s"], algorithmic_bytes=nbytes,
+                   hbm_fraction_of_8TBps=nbytes / d["wall_s"] / HBM_PEAK,
+                   us_per_T_dof_and_step_of_a_lane=d["wall_s"] / args.steps / (2 * n_cells) * 1e6,
+                   cg_ensemble=dict(c, bar_steps_per_s=bar_steps / c["wall_s"], algorithmic_bytes=cg_bytes),
+                   dg_over_cg_time=d["wall_s"] / c["wall_s"], dg_over_cg_algorithmic_bytes=nbytes / cg_bytes)
+        rows.append(row)
+        print(f"DG ensemble {d['n_bars']:6d} bars: {d['wall_s'] * 1e3:9.2f} ms  {row['bar_steps_per_s']:12.4g} "
+              f"bar-steps/s  {d['newton_its_per_step']:.2f} its/step  {row['hbm_fraction_of_8TBps']:.2%} of HBM peak;  "
+              f"CG {c['wall_s'] * 1e3:9.2f} ms  time ratio {row['dg_over_cg_time']:.3f}  "
+              f"byte ratio {row['dg_over_cg_algorithmic_bytes']:.3f}", flush=True)
+
+    def single(htc, steps):  # the same bar, DG / CG, one context per bar
+        prob = ThermoViscoProblem(mesh, span, 0.1, CFG_DG, dict(model_params, htc=float(htc)), verbose=False,
+                                  write_output=False)
+        prob.setup()
+        t0 = time.perf_counter()
+        prob.solve(steps)
+        prob.get_field("T")  # waits for the queued work
+        wall = time.perf_counter() - t0
+        prob.close()
+        return wall
+
+    single(280.1, 5)
+    seq_wall = sum(single(htc, args.steps) for htc in np.linspace(50.0, 1000.0, args.seq_bars))
+    seq_rate = args.seq_bars * args.steps / seq_wall
+    print(f"sequential {args.seq_bars} DG/CG bars: {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
+    for r in rows:
+        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
+    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "n_cells": n_cells,
+                        "n_dofs_T": 2 * n_cells, "steps": args.steps, "dt": 0.1, "htc": "linspace(50, 1000, n_bars)",
+                        "families": "DG1/CG1", "reps": args.reps},
+           "bytes_model": {"per_cell_newton_iteration": DG_BYTES_CELL_NEWTON, "per_T_dof_step": DG_BYTES_TDOF_STEP,
+                           "per_node_step": DG_BYTES_NODE_STEP},
+           "kernel": DG_KERNEL_RECORD, "ensemble": rows,
+           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
+                          "timed": "ThermoViscoProblem DG1/CG1: solve() and a final field read per bar; context "
+                                   "creation and setup left out"},
+           "floor_ratio_at_4096": FLOOR}
+    at = [r for r in rows if r["n_bars"] == 4096]
+    if at:
+        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
+        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
+    out = args.out or os.path.join(ROOT, "profiles", "ensemble_dg_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1)
+        fh.write("\n")
+    print(json.dumps({"out": out, "ratio_at_4096": res.get("ratio_at_4096")}))
+    if at and res["ratio_at_4096"] < FLOOR:
+        sys.exit(f"DG ensemble below the {FLOOR:g}x floor at 4096 bars")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 1024, 4096, 16384])
@@ -185,13 +294,18 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--seq-bars", type=int, default=4)
     ap.add_argument("--out", default=None, help="default profiles/ensemble_bench.json "
-                                                "(--scheduled: profiles/ensemble_schedule_bench.json)")
+                                                "(--scheduled: profiles/ensemble_schedule_bench.json, "
+                                                "--dg: profiles/ensemble_dg_bench.json)")
     ap.add_argument("--scheduled", action="store_true", help="the cost of a schedule and a history (see above)")
+    ap.add_argument("--dg", action="store_true",
+                    help="the DG1-temperature / CG1-stress ensemble against its sequential path and the CG ensemble")
     ap.add_argument("--parent-tree", default=None,
                     help="--scheduled: a built checkout of the parent commit; its own tools/ensemble_bench.py runs")
     args = ap.parse_args()
     if args.scheduled:
         return scheduled_bench(args)
+    if args.dg:
+        return dg_bench(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "ensemble_bench.json")
 
     from geometry import graded_bar
