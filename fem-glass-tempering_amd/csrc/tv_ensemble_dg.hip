@@ -1,22 +1,19 @@
 // Ensemble of independent 1D bars with DG1 temperature and CG1 stress (the
 // pairing of main.py's fe_config), gfx950: the whole time loop of thousands of
-// bars in one launch.  The CG1 / CG1 kernel is csrc/tv_ensemble.hip; this file
-// keeps its mapping and restates its step, stage and record logic.
+// bars in one launch.  This file holds the discretisation and its solver; the
+// step, Newton and record logic, the failure contract and the mapping are
+// csrc/tv_ensemble_step.h, shared with the CG1 / CG1 kernel (csrc/tv_ensemble.hip).
 //
-// Mapping: one lane per bar, a wave = 64 consecutive bars, one wave per
-// workgroup.  No LDS, no barriers, no cross-lane operations: a bar computes the
-// same bits alone or in any ensemble.  Layout: bar-fastest, [component][dof][bar]
-// (EnsArgs; n_nodes counts the mesh nodes, nS = n_nodes sigma dofs and
-// nT = 2 (n_nodes - 1) temperature dofs per bar), every load / store of a wave
-// one contiguous 512-byte segment.  T dofs are numbered 2 c + l (cell c, local
-// vertex l), the oracle's DG dofmap.
+// EnsArgs' n_nodes counts the mesh nodes: nS = n_nodes sigma dofs and
+// nT = 2 (n_nodes - 1) temperature dofs per bar.  T dofs are numbered 2 c + l
+// (cell c, local vertex l), the oracle's DG dofmap.
 //
-// Per step and lane (oracle/tv_oracle.py, HeatForm on a DG1 interval mesh),
+// Per Newton iteration and lane (oracle/tv_oracle.py, HeatForm on a DG1 interval mesh),
 // with a_c = T[2c], b_c = T[2c+1], cm = h_c / 6, ck = dt alpha / h_c:
 //   cell     mass cm [2 1; 1 2] (T - T_prev), stiffness ck [1 -1; -1 1] T,
 //            source -dt f h / 2 per dof;
 //   Robin    at dof 0 and dof nT - 1, dt 0.001 (sigma eps (T^4 - Ta^4) + htc (T - Ta))
-//            and its derivative on the diagonal (set_boundary of the CG kernel);
+//            and its derivative on the diagonal (set_boundary);
 //   SIPG     per interior node between cell c ('+', the lower index: penalty
 //            5 / h_c) and cell c + 1, with j = b_c - a_{c+1} and G_c = ck_c (b_c - a_c)
 //            (dt alpha times the cell's gradient):
@@ -32,22 +29,16 @@
 //            the 2x2 inverse by adjugate and determinant (one division per
 //            cell), the rows assembled inside the sweep; C_c and d_c go to the
 //            scratch [6][n_cells][bar]; the back sweep forms dx_c = d_c - C_c dx_{c+1},
-//            rewrites T <- T - dx and accumulates ||dx||^2;
-//   Newton   as k_ensemble: iteration 1 records ||dx_1||, afterwards converged
-//            iff ||dx|| / ||dx_1|| < rtol or ||dx|| < atol, at most max_it;
-//   visco    t_part at dof 2c, s_part at sigma node c with that state; t_part
-//            at dof 2c + 1, and for the last cell s_part at node n_cells with
-//            it (the oracle's sigma <- T map, "last cell in cell order wins":
-//            src(i) = 2 i, src(n_cells) = 2 n_cells - 1); then T_prev <- T.
-// Failure contract, thermal_only, statistics, schedules and probe records are
-// those of k_ensemble; a probe is a mesh node, T and Tf are recorded at its
-// source dof and sigma at the node.
+//            rewrites T <- T - dx and accumulates ||dx||^2.
+// The sigma <- T map is the oracle's, "last cell in cell order wins":
+// src(i) = 2 i, src(n_cells) = 2 n_cells - 1.  So dof 2c feeds sigma node c,
+// the last dof feeds node n_cells, and a probe (a mesh node) reads T and Tf at
+// src(node).
 //
 // No address depends on the recurrences: the forward sweep walks the cells in
 // chunks of kChunk, the back substitution in chunks of kChunkB, and each issues
 // the loads of the next chunk before the chain of the current one.
-#include "tv_internal.h"
-#include "tv_visco_point.h"
+#include "tv_ensemble_step.h"
 
 namespace tv {
 namespace {
@@ -56,8 +47,16 @@ namespace {
 // back substitution (2 / 2 takes 252 VGPRs and, in the kExt instantiation, one wave per SIMD)
 constexpr int kChunk = 2, kChunkB = 1;
 
-struct Bar {
-  double a_rad, a_conv, T_amb, T_amb4, dt, dtf;
+struct Dg1 {
+  static __device__ __forceinline__ int n_T(const EnsArgs& a) { return 2 * (a.n_nodes - 1); }
+  // dof 2 c is the source of sigma node c, dof nT - 1 that of node n_cells; the other odd dofs feed no node
+  static __device__ __forceinline__ int sigma_node(const EnsArgs& a, int i) {
+    return (i & 1) == 0 ? i >> 1 : (i == n_T(a) - 1 ? a.n_nodes - 1 : -1);
+  }
+  static __device__ __forceinline__ int source_dof(const EnsArgs& a, int node) {
+    return node < a.n_nodes - 1 ? 2 * node : n_T(a) - 1;
+  }
+  static __device__ __forceinline__ double newton_iteration(const EnsArgs& a, const Bar& b, int64_t bar);
 };
 
 // T, T_prev and the coefficients of cells base + 1 .. base + kChunk, the cell
@@ -105,7 +104,7 @@ __device__ __forceinline__ void load_back(const EnsArgs& a, int64_t bar, int top
 
 // One Newton iteration: assemble F(T) and J(T) cell by cell inside the block
 // forward elimination, back-substitute, T <- T - dx.  Returns ||dx||^2.
-__device__ __forceinline__ double newton_iteration(const EnsArgs& a, const Bar& b, int64_t bar) {
+__device__ __forceinline__ double Dg1::newton_iteration(const EnsArgs& a, const Bar& b, int64_t bar) {
   const int nc = a.n_nodes - 1;
   const int64_t plane = (int64_t)nc * a.nb_pad;
   // ---- forward sweep
@@ -207,105 +206,10 @@ __device__ __forceinline__ double newton_iteration(const EnsArgs& a, const Bar& 
   return nrm2;
 }
 
-// The bar's Robin coefficients from its (current stage's) htc, T_ambient, epsilon
-__device__ __forceinline__ void set_boundary(Bar& b, double sigma_sb, double htc, double Ta, double eps) {
-  const double Ta2 = Ta * Ta;
-  b.a_rad = 0.001 * (sigma_sb * eps);
-  b.a_conv = 0.001 * htc;
-  b.T_amb = Ta;
-  b.T_amb4 = Ta2 * Ta2;
-}
-
-// kExt as in k_ensemble: false = constant boundary values, final state only
-// (x is not read); true = per-bar stage tables and / or probe records (EnsExt).
 template <bool kExt>
 __global__ __launch_bounds__(kWave) void k_ensemble_dg(EnsArgs a, ViscoConst c, ViscoFields f,
                                                        const EnsExt* __restrict__ x) {
-  const int64_t bar = blockIdx.x * (int64_t)kWave + threadIdx.x;
-  if (bar >= a.n_bars) return;          // tail lanes: no memory access
-  if (a.failed_step[bar] != 0) return;  // frozen by an earlier failure
-  const int nc = a.n_nodes - 1, nT = 2 * nc;
-  Bar b;
-  set_boundary(b, a.sigma_sb, a.htc[bar], a.T_amb[bar], a.eps[bar]);
-  b.dt = a.dt;
-  b.dtf = a.dt * a.f[bar];
-  // kExt: the bar's stage and that stage's last step (the host has dropped the
-  // empty stages of each bar and closed its list with INT32_MAX)
-  int stage = 0, stage_last = INT32_MAX;
-  if constexpr (kExt) {
-    if (x->n_stages > 0) {
-      stage_last = x->stage_end[bar];
-      while (a.step_base + 1 > stage_last) {  // ends at the latest in the bar's last row (INT32_MAX)
-        ++stage;
-        stage_last = x->stage_end[(int64_t)stage * a.nb_pad + bar];
-      }
-      const int64_t t = (int64_t)stage * a.nb_pad + bar;
-      set_boundary(b, a.sigma_sb, x->htc[t], x->T_amb[t], x->eps[t]);
-    }
-  }
-  int its = 0, failed = 0;
-  int64_t total = 0;
-  for (int s = 0; s < a.n_steps; ++s) {
-    if constexpr (kExt) {
-      if (a.step_base + s + 1 > stage_last) {
-        ++stage;
-        const int64_t t = (int64_t)stage * a.nb_pad + bar;
-        stage_last = x->stage_end[t];
-        set_boundary(b, a.sigma_sb, x->htc[t], x->T_amb[t], x->eps[t]);
-      }
-    }
-    its = 0;
-    bool conv = false;
-    double r0 = 0.0;
-    while (!conv && its < a.max_it) {
-      const double r = sqrt(newton_iteration(a, b, bar));
-      ++its;
-      if (its == 1) {
-        r0 = r;
-      } else {
-        const double rel = r / r0;  // r0 == 0: NaN (r == 0) or inf, never < rtol
-        conv = rel < a.rtol || r < a.atol;
-      }
-    }
-    total += its;
-    if (!conv) {  // the step does not end: T <- T_prev, visco state untouched
-      for (int i = 0; i < nT; ++i) a.T[(int64_t)i * a.nb_pad + bar] = a.Tp[(int64_t)i * a.nb_pad + bar];
-      failed = a.step_base + s + 1;
-      break;
-    }
-    if (a.thermal_only) {
-      for (int i = 0; i < nT; ++i) a.Tp[(int64_t)i * a.nb_pad + bar] = a.T[(int64_t)i * a.nb_pad + bar];
-    } else {
-      bool dirty = false;  // LEAN bookkeeping of s_part, unused here
-      // dof 2 c is the source of sigma node c, dof nT - 1 that of node n_cells; the other odd dofs feed no node
-      for (int i = 0; i < nT; ++i) {
-        const int64_t t = (int64_t)i * a.nb_pad + bar;
-        const TState ts = t_part<false, false>(c, f, t);
-        const int node = (i & 1) == 0 ? i >> 1 : (i == nT - 1 ? nc : -1);  // wave-uniform
-        if (node >= 0) s_part<1, false, false>(c, f, (int64_t)node * a.nb_pad + bar, ts, dirty);
-        f.Tp[t] = ts.T;
-      }
-    }
-    if constexpr (kExt) {
-      // record step / every - 1 of [record][field][probe][bar]: T and Tf at the probe node's source dof,
-      // sigma at the node (the host refuses steps past max_records * every; the bound here only keeps
-      // the stores inside)
-      const int step = a.step_base + s + 1;
-      if (x->n_probes > 0 && step % x->every == 0 && step / x->every <= x->max_records) {
-        const int64_t rec = (int64_t)(step / x->every - 1) * 3 * x->n_probes;
-        for (int p = 0; p < x->n_probes; ++p) {
-          const int node = x->probes[p];
-          const int64_t t = (int64_t)(node < nc ? 2 * node : nT - 1) * a.nb_pad + bar;
-          x->hist[(rec + p) * a.nb_pad + bar] = a.T[t];
-          x->hist[(rec + x->n_probes + p) * a.nb_pad + bar] = f.Tf[t];
-          x->hist[(rec + 2 * x->n_probes + p) * a.nb_pad + bar] = f.sigma[(int64_t)node * a.nb_pad + bar];
-        }
-      }
-    }
-  }
-  a.its_last[bar] = its;
-  a.newton_total[bar] += total;
-  if (failed) a.failed_step[bar] = failed;
+  ensemble_bar<Dg1, kExt>(a, c, f, x);
 }
 
 }  // namespace

@@ -415,7 +415,8 @@ void launch_visco(int dim, int all, const ViscoConst& c, const ViscoFields& f, h
 void launch_visco_Tpass(int dim, int all, const ViscoConst& c, const ViscoFields& f, hipStream_t s);
 void launch_visco_Spass(int dim, int all, const ViscoConst& c, const ViscoFields& f, hipStream_t s);
 
-// ---- ensemble of independent 1D CG1 bars (tv_ensemble.hip) ----
+// ---- ensemble of independent 1D bars: the step shared by both temperature families is tv_ensemble_step.h,
+// the CG1 discretisation and solver tv_ensemble.hip, the DG1 ones tv_ensemble_dg.hip ----
 // One lane per bar; every per-bar array is bar-fastest, [component][node][bar]
 // with the bar count padded to a multiple of the wavefront (nb_pad), so element
 // (node i, bar b) of a field is i * nb_pad + b and a wave's loads and stores
@@ -462,8 +463,8 @@ struct EnsExt {
 };
 // x: device pointer, or nullptr for the plain kernel
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);
-// DG1 temperature with CG1 stress (tv_ensemble_dg.hip): the same arguments read as n_nodes mesh nodes =
-// sigma dofs and 2 (n_nodes - 1) T dofs (2 c + l) per bar, T / Tp [2 (n_nodes - 1)][nb_pad], scr
+// DG1 temperature with CG1 stress (tv_ensemble_dg.hip, the same step driver, ensemble_bar of
+// tv_ensemble_step.h, with another family struct): the same arguments read as n_nodes mesh nodes = sigma dofs and 2 (n_nodes - 1) T dofs (2 c + l) per bar, T / Tp [2 (n_nodes - 1)][nb_pad], scr
 // [6][n_nodes - 1][nb_pad] (C and d of the block elimination), ViscoFields with sT = 2 (n_nodes - 1) nb_pad
 // and sS = n_nodes nb_pad; EnsExt::probes stay mesh nodes
 void launch_ensemble_dg(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);

@@ -83,26 +83,25 @@ CFG_DG = {"T": {"element": "DG", "degree": 1}, "sigma": {"element": "CG", "degre
 DG_BYTES_CELL_NEWTON = 176
 DG_BYTES_TDOF_STEP = 144
 DG_BYTES_NODE_STEP = 200
-# the cross-compiler's resource report of csrc/tv_ensemble_dg.hip (gfx950, -O3 -ffp-contract=off); DESIGN.md
-# section 15, "DG temperature"
+# the cross-compiler's resource report of csrc/tv_ensemble_dg.hip and csrc/tv_ensemble.hip (gfx950, the Makefile's
+# flags: -O3 -ffp-contract=off), both instantiations of csrc/tv_ensemble_step.h; DESIGN.md section 15 says how it
+# is obtained.  scratch_instructions counts scratch loads / stores in the instruction stream.
 DG_KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 236, "sgpr_spill_count": 62, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 240, "sgpr_spill_count": 61, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 52, "scratch_instructions": 0,
+    "plain_instantiation": {"vgpr_count": 236, "sgpr_spill_count": 63, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                            "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 241, "sgpr_spill_count": 73, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
                                 "occupancy_waves_per_simd": 2},
 }
-# the cross-compiler's resource report of csrc/tv_ensemble.hip (gfx950, -O3 -ffp-contract=off), recorded with
-# the change that added schedules; DESIGN.md section 15 says how it was obtained
 KERNEL_RECORD = {
     "plain_instantiation": {"vgpr_count": 234, "sgpr_spill_count": 63, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0,
-                            "isa_vs_parent": "instruction stream identical up to the symbol name and block labels "
-                                             "(2074 lines); the kernarg segment grew by one unused pointer"},
-    "scheduled_instantiation": {"vgpr_count": 237, "sgpr_spill_count": 67, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 0, "occupancy_waves_per_simd": 2},
+                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                            "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 239, "sgpr_spill_count": 77, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                                "occupancy_waves_per_simd": 2},
 }
-
 
 def _time_ensembles(make, sizes, steps, reps):
     """Median / min / max wall time of solve(steps) over `reps` fresh ensembles per size, after a warm-up."""
@@ -124,6 +123,29 @@ def _time_ensembles(make, sizes, steps, reps):
         rows.append({"n_bars": n_bars, "wall_s": med, "wall_s_min": min(walls), "wall_s_max": max(walls),
                      "spread": (max(walls) - min(walls)) / med, "newton_its_per_step": its})
     return rows
+
+
+def _time_sequential(mesh, span, cfg, n, steps):
+    """`n` bars one after another through ThermoViscoProblem, htc spread as in the ensembles, one context per
+    bar, after a warm-up: (the time loops alone, the same with context creation and setup)."""
+    from main import model_params
+    from tvfem.problem import ThermoViscoProblem
+
+    def single(htc, steps):
+        prob = ThermoViscoProblem(mesh, span, 0.1, cfg, dict(model_params, htc=float(htc)), verbose=False,
+                                  write_output=False)
+        prob.setup()
+        t0 = time.perf_counter()
+        prob.solve(steps)
+        prob.get_field("T")  # waits for the queued work
+        wall = time.perf_counter() - t0
+        prob.close()
+        return wall
+
+    single(280.1, 5)
+    t0 = time.perf_counter()
+    wall = sum(single(htc, steps) for htc in np.linspace(50.0, 1000.0, n))
+    return wall, time.perf_counter() - t0
 
 
 def scheduled_bench(args):
@@ -213,7 +235,6 @@ def dg_bench(args):
     from geometry import graded_bar
     from main import model_params
     from tvfem import ThermoViscoEnsemble
-    from tvfem.problem import ThermoViscoProblem
 
     mesh = graded_bar()
     n_nodes = mesh.num_vertices
@@ -246,19 +267,7 @@ def dg_bench(args):
               f"CG {c['wall_s'] * 1e3:9.2f} ms  time ratio {row['dg_over_cg_time']:.3f}  "
               f"byte ratio {row['dg_over_cg_algorithmic_bytes']:.3f}", flush=True)
 
-    def single(htc, steps):  # the same bar, DG / CG, one context per bar
-        prob = ThermoViscoProblem(mesh, span, 0.1, CFG_DG, dict(model_params, htc=float(htc)), verbose=False,
-                                  write_output=False)
-        prob.setup()
-        t0 = time.perf_counter()
-        prob.solve(steps)
-        prob.get_field("T")  # waits for the queued work
-        wall = time.perf_counter() - t0
-        prob.close()
-        return wall
-
-    single(280.1, 5)
-    seq_wall = sum(single(htc, args.steps) for htc in np.linspace(50.0, 1000.0, args.seq_bars))
+    seq_wall, _ = _time_sequential(mesh, span, CFG_DG, args.seq_bars, args.steps)  # the same bar, DG / CG
     seq_rate = args.seq_bars * args.steps / seq_wall
     print(f"sequential {args.seq_bars} DG/CG bars: {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
     for r in rows:
@@ -311,7 +320,6 @@ def main():
     from geometry import graded_bar
     from main import model_params
     from tvfem import ThermoViscoEnsemble
-    from tvfem.problem import ThermoViscoProblem
 
     mesh = graded_bar()
     n_nodes = mesh.num_vertices
@@ -323,44 +331,18 @@ def main():
         return ens
 
     rows = []
-    for n_bars in args.sizes:
-        warm = ensemble(n_bars)
-        warm.solve(5)
-        warm.close()
-        walls, its = [], 0.0
-        for _ in range(args.reps):
-            ens = ensemble(n_bars)
-            t0 = time.perf_counter()
-            ens.solve(args.steps)  # returns after the device has finished
-            walls.append(time.perf_counter() - t0)
-            assert not ens.failed_step.any()
-            its = float(ens.newton_total.mean()) / args.steps
-            ens.close()
-        wall = statistics.median(walls)
+    for r in _time_ensembles(ensemble, args.sizes, args.steps, args.reps):
+        n_bars, wall, its = r["n_bars"], r["wall_s"], r["newton_its_per_step"]
         bar_steps = n_bars * args.steps
         nbytes = bar_steps * n_nodes * (BYTES_NODE_NEWTON * its + BYTES_NODE_STEP)
-        rows.append({"n_bars": n_bars, "wall_s": wall, "wall_s_min": min(walls), "wall_s_max": max(walls),
+        rows.append({"n_bars": n_bars, "wall_s": wall, "wall_s_min": r["wall_s_min"], "wall_s_max": r["wall_s_max"],
                      "bar_steps_per_s": bar_steps / wall, "newton_its_per_step": its,
                      "algorithmic_bytes": nbytes, "hbm_fraction_of_8TBps": nbytes / wall / HBM_PEAK})
         print(f"ensemble {n_bars:6d} bars: {wall * 1e3:9.2f} ms  {bar_steps / wall:12.4g} bar-steps/s  "
               f"{its:.2f} Newton its/step  {nbytes / wall / HBM_PEAK:.2%} of HBM peak", flush=True)
 
     # the same work one bar after another (what a parameter study costs without the ensemble)
-    def single(htc, steps):
-        prob = ThermoViscoProblem(mesh, span, 0.1, CFG, dict(model_params, htc=float(htc)), verbose=False,
-                                  write_output=False)
-        prob.setup()
-        t0 = time.perf_counter()
-        prob.solve(steps)
-        prob.get_field("T")  # waits for the queued work
-        wall = time.perf_counter() - t0
-        prob.close()
-        return wall
-
-    single(280.1, 5)
-    t0 = time.perf_counter()
-    seq_wall = sum(single(htc, args.steps) for htc in np.linspace(50.0, 1000.0, args.seq_bars))
-    seq_total = time.perf_counter() - t0
+    seq_wall, seq_total = _time_sequential(mesh, span, CFG, args.seq_bars, args.steps)
     seq_rate = args.seq_bars * args.steps / seq_wall  # the time loops alone: context creation left out
     print(f"sequential {args.seq_bars} bars: {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
     for r in rows:

@@ -8,7 +8,8 @@ src = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 else ""
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Iinclude",
        "-Ifem-glass-tempering_amd/csrc", "-c", src, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
-if "visco" in src:
+# the sources the Makefile builds without FMA contraction
+if re.search(r"tv_(visco|ensemble|ensemble_dg)\.hip$", src):
     cmd.insert(1, "-ffp-contract=off")
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
