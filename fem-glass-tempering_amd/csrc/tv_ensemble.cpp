@@ -3,6 +3,7 @@
 // stress) and csrc/tv_ensemble_dg.hip (DG1 temperature, CG1 stress: main.py's
 // own fe_config).  C-ABI: include/tvfem.h, tv_ensemble_*.
 //   tv_ensemble_create / _create_dg    ThermoViscoProblem.__init__ once per bar
+//   tv_ensemble_create_paper           the same with model_mode PAPER, either pairing
 //   tv_ensemble_set_initial_condition  _set_initial_condition (:187-233), each bar's T_0
 //   tv_ensemble_step                   n_steps x solve_timestep (:367-381) minus the
 //                                      file output, every bar, one launch per
@@ -119,10 +120,11 @@ int ens_push_ext(Ens* c) {
   return TV_OK;
 }
 
-// tv_ensemble_create (dg = false) and tv_ensemble_create_dg (dg = true): every refusal but the device's
-// is decided before the first HIP call
-int ens_create(const char* fn, bool dg, const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P,
-               const tv_options* opts, int device, void** ens_out) {
+// tv_ensemble_create (dg = false), tv_ensemble_create_dg (dg = true) and tv_ensemble_create_paper (paper:
+// model_mode PAPER required, refused by the other two): every refusal but the device's is decided before
+// the first HIP call
+int ens_create(const char* fn, bool dg, bool paper, const tv_ensemble_desc* d, const tv_fe_config* fe,
+               const tv_params* P, const tv_options* opts, int device, void** ens_out) {
   if (!d || !fe || !P || !ens_out) {
     set_global_error(std::string(fn) + ": null argument");
     return TV_ERR_ARG;
@@ -147,7 +149,14 @@ int ens_create(const char* fn, bool dg, const tv_ensemble_desc* d, const tv_fe_c
   c->dg = dg;
   if (opts) c->O = *opts;
   else tv_default_options(&c->O);
-  if (c->O.model_mode != TV_MODEL_REFERENCE) return bad("model_mode PAPER is not implemented for ensembles");
+  if (paper) {
+    if (!opts) return bad("options are required and must set model_mode PAPER (reference mode: tv_ensemble_create" +
+                          std::string(dg ? "_dg)" : ")"));
+    if (c->O.model_mode != TV_MODEL_PAPER)
+      return bad("model_mode must be PAPER (reference mode: tv_ensemble_create" + std::string(dg ? "_dg)" : ")"));
+  } else if (c->O.model_mode != TV_MODEL_REFERENCE) {
+    return bad("model_mode PAPER is not implemented for ensembles");
+  }
   if (!(P->dt > 0.0)) return bad("dt must be positive");
   if (c->O.newton_max_it < 1 || c->O.newton_rtol < 0.0 || c->O.newton_atol < 0.0)
     return bad("newton_max_it < 1 or a negative Newton tolerance");
@@ -209,6 +218,9 @@ int ens_create(const char* fn, bool dg, const tv_ensemble_desc* d, const tv_fe_c
                                   {TV_F_SIGMA_TILDE, 6, 1}};
   for (const auto& s : kState)
     if (rc == TV_OK) rc = ens_alloc_field(c.get(), s[0], s[1], s[2] ? nS : nT);
+  // paper mode: the partial stresses are state (Eq. 16 reads them back); zero as allocated, as in the oracle
+  if (paper && rc == TV_OK) rc = ens_alloc_field(c.get(), TV_F_S_PARTIAL, 6, nS);
+  if (paper && rc == TV_OK) rc = ens_alloc_field(c.get(), TV_F_SIGMA_PARTIAL, 6, nS);
   if (rc == TV_OK) rc = ens_alloc(c.get(), par.size() * sizeof(double), &dpar);
   if (rc == TV_OK) rc = ens_alloc(c.get(), cell.size() * sizeof(double), &dcell);
   // Thomas scratch [2][n_nodes][pad]; DG: C and d of the block elimination, [6][n_cells][pad]
@@ -255,7 +267,7 @@ int ens_create(const char* fn, bool dg, const tv_ensemble_desc* d, const tv_fe_c
   k.dalpha = P->alpha_liquid - P->alpha_solid;
   k.inv_dim = 1.0;
   k.chi = 0.5;
-  k.paper = 0;
+  k.paper = paper ? 1 : 0;
   for (int i = 0; i < 6; ++i) {
     k.lambda_m[i] = P->lambda_m[i]; k.m_n[i] = P->m_n[i];
     k.lambda_g[i] = P->lambda_g[i]; k.g_n[i] = P->g_n[i];
@@ -270,6 +282,7 @@ int ens_create(const char* fn, bool dg, const tv_ensemble_desc* d, const tv_fe_c
   v.Tf = c->field[TV_F_TF]; v.Tfp = c->field[TV_F_TF_PARTIAL];
   v.st = c->field[TV_F_S_TILDE]; v.sgt = c->field[TV_F_SIGMA_TILDE];
   v.sigma = c->field[TV_F_SIGMA];
+  v.sp = c->field[TV_F_S_PARTIAL]; v.sgp = c->field[TV_F_SIGMA_PARTIAL];  // null on a reference handle
   {
     std::lock_guard<std::mutex> lk(g_ens_mu);
     g_ens_live.insert(c.get());
@@ -287,13 +300,21 @@ extern "C" {
 
 int tv_ensemble_create(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P, const tv_options* opts,
                        int device, void** ens_out) {
-  return ens_create("tv_ensemble_create", false, d, fe, P, opts, device, ens_out);
+  return ens_create("tv_ensemble_create", false, false, d, fe, P, opts, device, ens_out);
 }
 
 
 int tv_ensemble_create_dg(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P,
                           const tv_options* opts, int device, void** ens_out) {
-  return ens_create("tv_ensemble_create_dg", true, d, fe, P, opts, device, ens_out);
+  return ens_create("tv_ensemble_create_dg", true, false, d, fe, P, opts, device, ens_out);
+}
+
+
+int tv_ensemble_create_paper(const tv_ensemble_desc* d, const tv_fe_config* fe, const tv_params* P,
+                             const tv_options* opts, int device, void** ens_out) {
+  // the family decides the kernel; a pairing neither accepts gets the refusal of that family's constructor
+  const bool dg = fe && fe->T_family == TV_DG;
+  return ens_create("tv_ensemble_create_paper", dg, true, d, fe, P, opts, device, ens_out);
 }
 
 
@@ -330,6 +351,9 @@ int tv_ensemble_set_initial_condition(void* ens) {
   HIPC(hipMemcpyAsync(c->field[TV_F_T_PREV], v.data(), plane, hipMemcpyHostToDevice, c->stream));
   HIPC(hipMemcpyAsync(c->field[TV_F_TF], v.data(), plane, hipMemcpyHostToDevice, c->stream));
   HIPC(hipMemcpyAsync(c->field[TV_F_TF_PARTIAL], v.data(), 6 * plane, hipMemcpyHostToDevice, c->stream));
+  // a paper handle's stress memory starts at zero (the oracle's s_partial / sigma_partial)
+  for (int id : {TV_F_S_PARTIAL, TV_F_SIGMA_PARTIAL})
+    if (c->field[id]) HIPC(hipMemsetAsync(c->field[id], 0, sizeof(double) * 6 * c->nS * pad, c->stream));
   HIPC(hipStreamSynchronize(c->stream));
   return TV_OK;
 }

@@ -131,16 +131,24 @@ __device__ __forceinline__ double Cg1::newton_iteration(const EnsArgs& a, const 
   return nrm2;
 }
 
-template <bool kExt>
-__global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, ViscoFields f, const EnsExt* __restrict__ x) {
-  ensemble_bar<Cg1, kExt>(a, c, f, x);
+template <bool kExt, bool kPaper>
+__global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, ViscoFields f,
+                                                    const EnsExt* __restrict__ x) {
+  ensemble_bar<Cg1, kExt, kPaper>(a, c, f, x);
 }
 
 }  // namespace
 
+// the model mode is the handle's (ViscoConst::paper), the scheduled instantiation runs when x is given
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s) {
-  if (x) hipLaunchKernelGGL(k_ensemble<true>, dim3(a.nb_pad / kWave), dim3(kWave), 0, s, a, c, f, x);
-  else hipLaunchKernelGGL(k_ensemble<false>, dim3(a.nb_pad / kWave), dim3(kWave), 0, s, a, c, f, nullptr);
+  const dim3 grid(a.nb_pad / kWave), block(kWave);
+  if (c.paper) {
+    if (x) hipLaunchKernelGGL((k_ensemble<true, true>), grid, block, 0, s, a, c, f, x);
+    else hipLaunchKernelGGL((k_ensemble<false, true>), grid, block, 0, s, a, c, f, nullptr);
+  } else {
+    if (x) hipLaunchKernelGGL((k_ensemble<true, false>), grid, block, 0, s, a, c, f, x);
+    else hipLaunchKernelGGL((k_ensemble<false, false>), grid, block, 0, s, a, c, f, nullptr);
+  }
 }
 
 }  // namespace tv

@@ -1,7 +1,7 @@
 // The time loop of one ensemble bar, shared by the CG1 (tv_ensemble.hip) and
 // DG1 (tv_ensemble_dg.hip) temperature kernels: everything of the ensemble's
 // contract towards tv_step and the oracle that does not depend on the
-// discretisation.  A kernel is ensemble_bar<Fam, kExt> and nothing else.
+// discretisation.  A kernel is ensemble_bar<Fam, kExt, kPaper> and nothing else.
 //
 // Mapping: one lane per bar, a wave = 64 consecutive bars, one wave per
 // workgroup (so a small ensemble spreads over the CUs).  No LDS, no barriers,
@@ -24,8 +24,13 @@
 //             (||dx_1|| = 0: the quotient is NaN or inf and atol decides, as
 //             in the oracle), at most max_it iterations;
 //   visco     t_part of tv_visco_point.h per T dof and s_part at the sigma
-//             node that dof feeds, with its state (D = 1, reference mode,
-//             stored s_tilde / sigma_tilde), then T_prev <- T.
+//             node that dof feeds, with its state (D = 1, stored s_tilde /
+//             sigma_tilde), then T_prev <- T.  kPaper selects the model mode
+//             of both and nothing else: in paper mode s_part also reads and
+//             rewrites s_partial / sigma_partial (ViscoFields::sp / sgp, state
+//             of a paper handle only), and the TState that t_part returns
+//             carries the dof's Tf of the previous step to the sigma node, so
+//             no Tfo work array exists.
 // A bar whose Newton solve ends unconverged gets T <- T_prev, keeps the visco
 // state of the previous step (tv_step's contract) and is frozen: failed_step
 // records the step and the lane does nothing from then on.  Lanes of a wave
@@ -67,7 +72,7 @@ __device__ __forceinline__ void set_boundary(Bar& b, double sigma_sb, double htc
 // no address pattern changes.
 // The structs come by value: by reference the scheduled CG kernel gains a
 // private segment.
-template <class Fam, bool kExt>
+template <class Fam, bool kExt, bool kPaper>
 __device__ __forceinline__ void ensemble_bar(EnsArgs a, ViscoConst c, ViscoFields f, const EnsExt* __restrict__ x) {
   const int64_t bar = blockIdx.x * (int64_t)kWave + threadIdx.x;
   if (bar >= a.n_bars) return;          // tail lanes: no memory access
@@ -128,9 +133,9 @@ __device__ __forceinline__ void ensemble_bar(EnsArgs a, ViscoConst c, ViscoField
       bool dirty = false;  // LEAN bookkeeping of s_part, unused here
       for (int i = 0; i < nT; ++i) {
         const int64_t t = (int64_t)i * a.nb_pad + bar;
-        const TState ts = t_part<false, false>(c, f, t);
+        const TState ts = t_part<false, kPaper>(c, f, t);
         const int node = Fam::sigma_node(a, i);
-        if (node >= 0) s_part<1, false, false>(c, f, (int64_t)node * a.nb_pad + bar, ts, dirty);
+        if (node >= 0) s_part<1, false, false, kPaper>(c, f, (int64_t)node * a.nb_pad + bar, ts, dirty);
         f.Tp[t] = ts.T;
       }
     }

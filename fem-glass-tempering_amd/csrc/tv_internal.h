@@ -461,7 +461,8 @@ struct EnsExt {
   const int* probes;          // [n_probes] node of each probe, the same for every bar
   double* hist;               // [max_records][3 (T, Tf, sigma)][n_probes][nb_pad]
 };
-// x: device pointer, or nullptr for the plain kernel
+// x: device pointer, or nullptr for the plain kernel; c.paper selects the paper-mode instantiations, which
+// read and write f.sp / f.sgp (state of a paper handle) besides
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);
 // DG1 temperature with CG1 stress (tv_ensemble_dg.hip, the same step driver, ensemble_bar of
 // tv_ensemble_step.h, with another family struct): the same arguments read as n_nodes mesh nodes = sigma dofs and 2 (n_nodes - 1) T dofs (2 c + l) per bar, T / Tp [2 (n_nodes - 1)][nb_pad], scr

@@ -44,7 +44,7 @@ EXPORTS = [
     "tv_ensemble_create", "tv_ensemble_destroy", "tv_ensemble_set_initial_condition", "tv_ensemble_step",
     "tv_ensemble_get_field", "tv_ensemble_set_field", "tv_ensemble_stats",
     "tv_ensemble_set_schedule", "tv_ensemble_history_open", "tv_ensemble_history_read",
-    "tv_ensemble_create_dg",
+    "tv_ensemble_create_dg", "tv_ensemble_create_paper",
     "tv_guard_check",
 ]
 
@@ -195,6 +195,8 @@ def load_library():
                                          C.POINTER(Options), C.c_int, C.POINTER(vp)]),
         "tv_ensemble_create_dg": (C.c_int, [C.POINTER(EnsembleDesc), C.POINTER(FeConfig), C.POINTER(Params),
                                             C.POINTER(Options), C.c_int, C.POINTER(vp)]),
+        "tv_ensemble_create_paper": (C.c_int, [C.POINTER(EnsembleDesc), C.POINTER(FeConfig), C.POINTER(Params),
+                                               C.POINTER(Options), C.c_int, C.POINTER(vp)]),
         "tv_ensemble_destroy": (C.c_int, [vp]),
         "tv_ensemble_set_initial_condition": (C.c_int, [vp]),
         "tv_ensemble_step": (C.c_int, [vp, C.c_int, C.c_int]),

@@ -5,7 +5,7 @@ A parameter study of the reference's own workload (main.py: one
 through-thickness bar): every bar has the same cell count and may have its
 own node coordinates (thickness, grading) and its own ``htc``, ``T_0``,
 ``T_ambient``, ``epsilon``, ``alpha`` and ``f``; ``dt`` and every other model
-parameter are shared.  Reference model mode; ``config`` is CG1 temperature with
+parameter are shared.  ``config`` is CG1 temperature with
 CG1 stress, or DG1 temperature with CG1 stress (main.py's own ``fe_config``: SIPG
 on the interior nodes, two T dofs per cell numbered ``2 c + l``).  With DG
 temperature the T-family fields (T, T_prev, Tf, Tf_partial, phi, xi) have
@@ -36,6 +36,28 @@ Every stage but the last carries exactly one of ``until`` (a time, on the step
 grid) or ``until_step``; step s (1-based) belongs to the first stage whose end
 is not before it, so equal ends give an empty stage.  The other keys are scalars
 or per-bar arrays; a missing key keeps the bar's ``model_parameters`` value.
+
+``model_mode="reference"`` (the default) computes what the reference code
+computes, quirks included.  ``model_mode="paper"`` runs the model as the paper
+states it, for either config, as ``ThermoViscoProblem(model_mode="paper")``:
+Eq. 25 (with Tf) drives Eq. 24 instead of being overwritten by Eq. 5 (Q1); the
+structural strain ``(alpha_liquid - alpha_solid) (Tf - Tf_prev)`` is kept (Q2);
+Eq. 16 feeds the stress memory from the previous partial stresses, so the
+stress has a history (Q3); and ``xi = dt/2 (phi_next + phi)``, so sigma is
+finite where T has not moved (Q4).  The thermal problem does not see the mode.
+A paper ensemble has two more state fields on the stress space, ``s_partial``
+and ``sigma_partial`` (block size 6, zero after ``setup()``); on a reference
+ensemble ``get_field`` / ``set_field`` of them raise (TV_ERR_STATE).
+
+Both modes keep the reference's degree-2 Taylor exponential ``E = 1 - x + x^2/2``,
+``x = xi / lambda``, which exceeds 1 when ``xi > 2 lambda``.  In paper mode ``xi``
+is no longer tiny and the stress memory is multiplied by ``E`` every step: with
+main.py's parameters and dt = 0.1 (smallest ``lambda_k`` 5.0e-5) a bar at
+``T_0 = 800 K`` stays inside the limit (``xi`` peaks at 7.0e-5) and is stable
+over 500 steps, while at 873 K ``xi`` is about 0.2 and sigma passes 1e23 after
+five steps and reaches +-inf within 100.  That is the model as the reference
+states it, not a defect of the kernel; a sweep over ``T_0`` must stay below the
+limit.  Such a bar harms no other bar of the ensemble.
 """
 from __future__ import annotations
 
@@ -50,10 +72,11 @@ from .mesh import RectilinearMesh
 # model parameters that may differ from bar to bar
 PER_BAR_KEYS = ("htc", "T_0", "T_ambient", "epsilon", "alpha", "f")
 # the state an ensemble keeps (names as ThermoViscoProblem.get_field) and its block size per dof
+# (s_partial and sigma_partial: paper ensembles only)
 STATE_FIELDS = {"T": 1, "T_prev": 1, "Tf": 1, "Tf_partial": 6, "phi": 1, "xi": 1, "sigma": 1,
-                "s_tilde_partial": 6, "sigma_tilde_partial": 6}
+                "s_tilde_partial": 6, "sigma_tilde_partial": 6, "s_partial": 6, "sigma_partial": 6}
 # the fields that live on the stress space (every other state field lives on the temperature space)
-SIGMA_FAMILY = ("sigma", "s_tilde_partial", "sigma_tilde_partial")
+SIGMA_FAMILY = ("sigma", "s_tilde_partial", "sigma_tilde_partial", "s_partial", "sigma_partial")
 _FAMILIES = {"CG": N.TV_CG, "DG": N.TV_DG}
 # what a schedule stage may change, and how it says where it ends
 STAGE_KEYS = ("htc", "T_ambient", "epsilon")
@@ -130,6 +153,7 @@ class ThermoViscoEnsemble:
         self.t = self.time[0]
         self.n_steps = ceil((self.time[1] - self.time[0]) / self.dt)
         self.config = config
+        self.model_mode = model_mode
         # DG1 temperature with CG1 stress has its own kernel and constructor; every other pairing goes to
         # tv_ensemble_create, which accepts CG1 / CG1 and refuses the rest
         self._dg = (config["T"]["element"] == "DG" and int(config["T"]["degree"]) == 1
@@ -166,7 +190,11 @@ class ThermoViscoEnsemble:
             opts.newton_max_it = newton_max_it
         opts.error_on_nonconvergence = 1 if error_on_nonconvergence else 0
         ens = C.c_void_p()
-        create = lib.tv_ensemble_create_dg if self._dg else lib.tv_ensemble_create
+        # paper mode has one constructor for both pairings (the family is read from fe)
+        if model_mode == "paper":
+            create = lib.tv_ensemble_create_paper
+        else:
+            create = lib.tv_ensemble_create_dg if self._dg else lib.tv_ensemble_create
         N.check(create(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), device, C.byref(ens)))
         self._ens = ens
         try:

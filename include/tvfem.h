@@ -61,7 +61,7 @@ extern "C" {
                             8: tv_options lost the unused use_graphs field;
                                (still 8, additions only: tv_ensemble_desc and the tv_ensemble_* functions;
                                then tv_ensemble_schedule, tv_ensemble_set_schedule, tv_ensemble_history_*;
-                               then tv_ensemble_create_dg) */
+                               then tv_ensemble_create_dg; then tv_ensemble_create_paper) */
 
 /* status codes */
 #define TV_OK 0
@@ -443,9 +443,34 @@ int tv_ensemble_create(const tv_ensemble_desc* desc, const tv_fe_config* fe, con
  * src(n_cells) = 2 n_cells - 1 (the last cell in cell order wins). */
 int tv_ensemble_create_dg(const tv_ensemble_desc* desc, const tv_fe_config* fe, const tv_params* shared,
                           const tv_options* opts, int device, void** ens_out);
+/* The same bars in paper model mode (TV_MODEL_PAPER, as tv_create: Eq. 25
+ * drives Eq. 24, the structural strain alpha_l - alpha_s times Tf - Tf_prev is
+ * kept, Eq. 16 feeds the stress memory from s_partial / sigma_partial, xi is
+ * the trapezoidal sum -- the quirks Q1-Q4 of the reference fixed), for either
+ * pairing: fe selects T = CG1 (the kernel of tv_ensemble_create) or T = DG1
+ * (that of tv_ensemble_create_dg), sigma = CG1.  opts must be given with
+ * model_mode == TV_MODEL_PAPER: NULL or REFERENCE returns TV_ERR_ARG and names
+ * the constructor to use (the two above keep refusing PAPER).  Every other
+ * refusal is that of the family's constructor, before the GPU is touched.
+ * A paper handle has two more state fields on the sigma family, TV_F_S_PARTIAL
+ * and TV_F_SIGMA_PARTIAL (bs 6, nS dofs), zero at creation and after
+ * tv_ensemble_set_initial_condition; on a reference handle those two ids stay
+ * TV_ERR_STATE.  Every other tv_ensemble_* function takes the handle; the
+ * thermal problem, schedules, histories, statistics and the failure contract
+ * do not depend on the mode.
+ * Both modes keep the reference's degree-2 _taylor_exponential
+ * E = 1 - x + x^2 / 2, x = xi / lambda, which exceeds 1 for xi > 2 lambda.  In
+ * paper mode xi = dt / 2 (phi_next + phi) is not tiny and the stress memory is
+ * multiplied by E every step: with main.py's parameters and dt = 0.1 (smallest
+ * lambda_k 5.0e-5) a bar at T_0 = 800 K stays inside the limit (xi <= 7.0e-5),
+ * one at 873 K (xi ~ 0.2) overflows to +-inf within 100 steps.  That is the
+ * model as the reference states it; such a bar harms no other lane. */
+int tv_ensemble_create_paper(const tv_ensemble_desc* desc, const tv_fe_config* fe, const tv_params* shared,
+                             const tv_options* opts, int device, void** ens_out);
 int tv_ensemble_destroy(void* ens);
 /* T = T_prev = Tf = Tf_partial = each bar's own T_0 (as tv_set_initial_condition;
- * the other fields and the Newton / failure records keep their values) */
+ * the other fields and the Newton / failure records keep their values); a
+ * paper handle's S_PARTIAL and SIGMA_PARTIAL go back to zero */
 int tv_ensemble_set_initial_condition(void* ens);
 /* n_steps time steps of every bar (several launches when n_steps x nodes is
  * large); returns when they have finished.  A bar whose Newton solve reaches
@@ -458,7 +483,8 @@ int tv_ensemble_set_initial_condition(void* ens);
 int tv_ensemble_step(void* ens, int n_steps, int thermal_only);
 /* host <-> device, [bar][dof*bs + comp] (per bar the reference's interleaved
  * layout); fields: TV_F_T, T_PREV, TF, TF_PARTIAL, PHI, XI, SIGMA, S_TILDE,
- * SIGMA_TILDE -- every other id returns TV_ERR_STATE */
+ * SIGMA_TILDE, and on a paper handle S_PARTIAL and SIGMA_PARTIAL -- every
+ * other id returns TV_ERR_STATE */
 int tv_ensemble_get_field(void* ens, int field, double* host, size_t n_values);
 int tv_ensemble_set_field(void* ens, int field, const double* host, size_t n_values);
 /* per bar (n_bars values each, any pointer may be NULL): Newton iterations of

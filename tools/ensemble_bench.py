@@ -56,6 +56,24 @@ the DG / CG time ratio beside the ratio of the algorithmic bytes:
                                         them and sigma
 
 The same 64x floor at 4096 bars holds; the tool exits non-zero below it.
+
+--paper measures the paper model mode (model_mode="paper", the kPaper
+instantiations of both kernels; default output
+profiles/ensemble_paper_bench.json, one key per pairing), CG1 / CG1 or with --dg
+DG1 / CG1: the same
+bar, parameters (T_0 = 800 K, inside the Taylor limit) and sizes, in one run the
+paper ensemble, the reference-mode ensemble and --seq-bars (default here: 1)
+paper-mode bars through ThermoViscoProblem(model_mode="paper"); per size the
+paper / reference time ratio beside the ratio of the algorithmic bytes.  Paper
+mode adds to the viscoelastic update one read of Tf per T dof and twelve
+written partial stresses per node:
+
+  CG   per node and step      448 B  (reference 344 B)
+  DG   per T dof and step     152 B  (reference 144 B)
+       per mesh node and step 296 B  (reference 200 B)
+
+The ratios are recorded, not judged; the 64x floor at 4096 bars against the
+paper-mode sequential path holds, and the tool exits non-zero below it.
 """
 import argparse
 import json
@@ -103,6 +121,28 @@ KERNEL_RECORD = {
                                 "occupancy_waves_per_simd": 2},
 }
 
+PAPER_BYTES_NODE_STEP = 448
+PAPER_DG_BYTES_TDOF_STEP = 152
+PAPER_DG_BYTES_NODE_STEP = 296
+# the kPaper instantiations, obtained the same way (tools/kres.py)
+PAPER_KERNEL_RECORD = {
+    "plain_instantiation": {"vgpr_count": 233, "sgpr_spill_count": 82, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                            "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 237, "sgpr_spill_count": 96, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
+                                "occupancy_waves_per_simd": 2},
+}
+PAPER_DG_KERNEL_RECORD = {
+    "plain_instantiation": {"vgpr_count": 238, "sgpr_spill_count": 61, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                            "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 243, "sgpr_spill_count": 79, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
+                                "occupancy_waves_per_simd": 2},
+}
+
+
 def _time_ensembles(make, sizes, steps, reps):
     """Median / min / max wall time of solve(steps) over `reps` fresh ensembles per size, after a warm-up."""
     rows = []
@@ -125,7 +165,7 @@ def _time_ensembles(make, sizes, steps, reps):
     return rows
 
 
-def _time_sequential(mesh, span, cfg, n, steps):
+def _time_sequential(mesh, span, cfg, n, steps, **problem_kw):
     """`n` bars one after another through ThermoViscoProblem, htc spread as in the ensembles, one context per
     bar, after a warm-up: (the time loops alone, the same with context creation and setup)."""
     from main import model_params
@@ -133,7 +173,7 @@ def _time_sequential(mesh, span, cfg, n, steps):
 
     def single(htc, steps):
         prob = ThermoViscoProblem(mesh, span, 0.1, cfg, dict(model_params, htc=float(htc)), verbose=False,
-                                  write_output=False)
+                                  write_output=False, **problem_kw)
         prob.setup()
         t0 = time.perf_counter()
         prob.solve(steps)
@@ -296,21 +336,115 @@ def dg_bench(args):
         sys.exit(f"DG ensemble below the {FLOOR:g}x floor at 4096 bars")
 
 
+def paper_bench(args):
+    from geometry import graded_bar
+    from main import model_params
+    from tvfem import ThermoViscoEnsemble
+
+    mesh = graded_bar()
+    n_nodes = mesh.num_vertices
+    n_cells = n_nodes - 1
+    span = (0.0, args.steps * 0.1)
+    cfg = CFG_DG if args.dg else CFG
+    families = "DG1/CG1" if args.dg else "CG1/CG1"
+
+    def make(mode):
+        def ensemble(n_bars):
+            ens = ThermoViscoEnsemble(mesh, span, 0.1, cfg, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)),
+                                      model_mode=mode)
+            ens.setup()
+            return ens
+        return ensemble
+
+    def model_bytes(its, paper):
+        if args.dg:
+            return (n_cells * DG_BYTES_CELL_NEWTON * its
+                    + 2 * n_cells * (PAPER_DG_BYTES_TDOF_STEP if paper else DG_BYTES_TDOF_STEP)
+                    + n_nodes * (PAPER_DG_BYTES_NODE_STEP if paper else DG_BYTES_NODE_STEP))
+        return n_nodes * (BYTES_NODE_NEWTON * its + (PAPER_BYTES_NODE_STEP if paper else BYTES_NODE_STEP))
+
+    pap = _time_ensembles(make("paper"), args.sizes, args.steps, args.reps)
+    ref = _time_ensembles(make("reference"), args.sizes, args.steps, args.reps)
+    rows = []
+    for p, r in zip(pap, ref):
+        bar_steps = p["n_bars"] * args.steps
+        nbytes = bar_steps * model_bytes(p["newton_its_per_step"], True)
+        ref_bytes = bar_steps * model_bytes(r["newton_its_per_step"], False)
+        row = dict(p, bar_steps_per_s=bar_steps / p["wall_s"], algorithmic_bytes=nbytes,
+                   hbm_fraction_of_8TBps=nbytes / p["wall_s"] / HBM_PEAK,
+                   reference_ensemble=dict(r, bar_steps_per_s=bar_steps / r["wall_s"], algorithmic_bytes=ref_bytes),
+                   paper_over_reference_time=p["wall_s"] / r["wall_s"],
+                   paper_over_reference_algorithmic_bytes=nbytes / ref_bytes)
+        rows.append(row)
+        print(f"paper {families} ensemble {p['n_bars']:6d} bars: {p['wall_s'] * 1e3:9.2f} ms  "
+              f"{row['bar_steps_per_s']:12.4g} bar-steps/s  {p['newton_its_per_step']:.2f} its/step  "
+              f"{row['hbm_fraction_of_8TBps']:.2%} of HBM peak;  reference {r['wall_s'] * 1e3:9.2f} ms  "
+              f"time ratio {row['paper_over_reference_time']:.3f}  "
+              f"byte ratio {row['paper_over_reference_algorithmic_bytes']:.3f}", flush=True)
+
+    seq_wall, _ = _time_sequential(mesh, span, cfg, args.seq_bars, args.steps, model_mode="paper")
+    seq_rate = args.seq_bars * args.steps / seq_wall
+    print(f"sequential {args.seq_bars} paper-mode {families} bar(s): {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s",
+          flush=True)
+    for r in rows:
+        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
+    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "n_cells": n_cells, "steps": args.steps,
+                        "dt": 0.1, "htc": "linspace(50, 1000, n_bars)", "T_0": model_params["T_0"],
+                        "families": families, "model_mode": "paper", "reps": args.reps},
+           "bytes_model": ({"per_cell_newton_iteration": DG_BYTES_CELL_NEWTON,
+                            "per_T_dof_step": PAPER_DG_BYTES_TDOF_STEP, "per_node_step": PAPER_DG_BYTES_NODE_STEP,
+                            "reference_per_T_dof_step": DG_BYTES_TDOF_STEP,
+                            "reference_per_node_step": DG_BYTES_NODE_STEP} if args.dg else
+                           {"per_node_newton_iteration": BYTES_NODE_NEWTON, "per_node_step": PAPER_BYTES_NODE_STEP,
+                            "reference_per_node_step": BYTES_NODE_STEP}),
+           "kernel": PAPER_DG_KERNEL_RECORD if args.dg else PAPER_KERNEL_RECORD, "ensemble": rows,
+           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
+                          "timed": f"ThermoViscoProblem {families} model_mode=paper: solve() and a final field read "
+                                   "per bar; context creation and setup left out"},
+           "floor_ratio_at_4096": FLOOR}
+    at = [r for r in rows if r["n_bars"] == 4096]
+    if at:
+        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
+        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
+    # one file for both pairings, keyed by the families: a run replaces its own key and keeps the other
+    out = args.out or os.path.join(ROOT, "profiles", "ensemble_paper_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    both = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            both = json.load(fh)
+    both[families] = res
+    with open(out, "w") as fh:
+        json.dump(both, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(json.dumps({"out": out, "ratio_at_4096": res.get("ratio_at_4096")}))
+    if at and res["ratio_at_4096"] < FLOOR:
+        sys.exit(f"paper ensemble below the {FLOOR:g}x floor at 4096 bars")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 1024, 4096, 16384])
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--seq-bars", type=int, default=4)
+    ap.add_argument("--seq-bars", type=int, default=None, help="default 4 (--paper: 1)")
     ap.add_argument("--out", default=None, help="default profiles/ensemble_bench.json "
                                                 "(--scheduled: profiles/ensemble_schedule_bench.json, "
-                                                "--dg: profiles/ensemble_dg_bench.json)")
+                                                "--dg: profiles/ensemble_dg_bench.json, "
+                                                "--paper: profiles/ensemble_paper_bench.json)")
     ap.add_argument("--scheduled", action="store_true", help="the cost of a schedule and a history (see above)")
     ap.add_argument("--dg", action="store_true",
                     help="the DG1-temperature / CG1-stress ensemble against its sequential path and the CG ensemble")
     ap.add_argument("--parent-tree", default=None,
                     help="--scheduled: a built checkout of the parent commit; its own tools/ensemble_bench.py runs")
+    ap.add_argument("--paper", action="store_true",
+                    help="the paper-mode ensemble (with --dg: DG1 / CG1) against the reference-mode ensemble and "
+                         "its own sequential path")
     args = ap.parse_args()
+    if args.seq_bars is None:
+        args.seq_bars = 1 if args.paper else 4
+    if args.paper:
+        return paper_bench(args)
     if args.scheduled:
         return scheduled_bench(args)
     if args.dg:
