@@ -716,6 +716,11 @@ int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params*
   c->P = *params;
   if (opts) c->O = *opts;
   else tv_default_options(&c->O);
+  if (c->O.model_mode == TV_MODEL_PAPER_EXACT) {
+    set_global_error("tv_create: model_mode PAPER_EXACT: the exact relaxation exists for ensembles only "
+                     "(tv_ensemble_create_paper)");
+    return TV_ERR_ARG;
+  }
   c->device = device;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -843,6 +848,11 @@ static int create_unstructured(const tv_umesh_desc* mesh, const tv_upart_desc* p
   c->P = *params;
   if (opts) c->O = *opts;
   else tv_default_options(&c->O);
+  if (c->O.model_mode == TV_MODEL_PAPER_EXACT) {
+    set_global_error("tv_create_unstructured: model_mode PAPER_EXACT: the exact relaxation exists for ensembles "
+                     "only (tv_ensemble_create_paper)");
+    return TV_ERR_ARG;
+  }
   c->device = device;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {

@@ -3,7 +3,7 @@
 // stress) and csrc/tv_ensemble_dg.hip (DG1 temperature, CG1 stress: main.py's
 // own fe_config).  C-ABI: include/tvfem.h, tv_ensemble_*.
 //   tv_ensemble_create / _create_dg    ThermoViscoProblem.__init__ once per bar
-//   tv_ensemble_create_paper           the same with model_mode PAPER, either pairing
+//   tv_ensemble_create_paper           the same with model_mode PAPER or PAPER_EXACT, either pairing
 //   tv_ensemble_set_initial_condition  _set_initial_condition (:187-233), each bar's T_0
 //   tv_ensemble_step                   n_steps x solve_timestep (:367-381) minus the
 //                                      file output, every bar, one launch per
@@ -121,8 +121,8 @@ int ens_push_ext(Ens* c) {
 }
 
 // tv_ensemble_create (dg = false), tv_ensemble_create_dg (dg = true) and tv_ensemble_create_paper (paper:
-// model_mode PAPER required, refused by the other two): every refusal but the device's is decided before
-// the first HIP call
+// model_mode PAPER or PAPER_EXACT required, both refused by the other two): every refusal but the device's
+// is decided before the first HIP call
 int ens_create(const char* fn, bool dg, bool paper, const tv_ensemble_desc* d, const tv_fe_config* fe,
                const tv_params* P, const tv_options* opts, int device, void** ens_out) {
   if (!d || !fe || !P || !ens_out) {
@@ -152,11 +152,12 @@ int ens_create(const char* fn, bool dg, bool paper, const tv_ensemble_desc* d, c
   if (paper) {
     if (!opts) return bad("options are required and must set model_mode PAPER (reference mode: tv_ensemble_create" +
                           std::string(dg ? "_dg)" : ")"));
-    if (c->O.model_mode != TV_MODEL_PAPER)
+    if (c->O.model_mode != TV_MODEL_PAPER && c->O.model_mode != TV_MODEL_PAPER_EXACT)
       return bad("model_mode must be PAPER (reference mode: tv_ensemble_create" + std::string(dg ? "_dg)" : ")"));
   } else if (c->O.model_mode != TV_MODEL_REFERENCE) {
     return bad("model_mode PAPER is not implemented for ensembles");
   }
+  const bool exact = paper && c->O.model_mode == TV_MODEL_PAPER_EXACT;
   if (!(P->dt > 0.0)) return bad("dt must be positive");
   if (c->O.newton_max_it < 1 || c->O.newton_rtol < 0.0 || c->O.newton_atol < 0.0)
     return bad("newton_max_it < 1 or a negative Newton tolerance");
@@ -267,7 +268,7 @@ int ens_create(const char* fn, bool dg, bool paper, const tv_ensemble_desc* d, c
   k.dalpha = P->alpha_liquid - P->alpha_solid;
   k.inv_dim = 1.0;
   k.chi = 0.5;
-  k.paper = paper ? 1 : 0;
+  k.paper = exact ? 2 : (paper ? 1 : 0);  // the kernels' model id
   for (int i = 0; i < 6; ++i) {
     k.lambda_m[i] = P->lambda_m[i]; k.m_n[i] = P->m_n[i];
     k.lambda_g[i] = P->lambda_g[i]; k.g_n[i] = P->g_n[i];

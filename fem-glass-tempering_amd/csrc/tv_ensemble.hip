@@ -131,23 +131,27 @@ __device__ __forceinline__ double Cg1::newton_iteration(const EnsArgs& a, const 
   return nrm2;
 }
 
-template <bool kExt, bool kPaper>
+template <bool kExt, int kModel>
 __global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, ViscoFields f,
                                                     const EnsExt* __restrict__ x) {
-  ensemble_bar<Cg1, kExt, kPaper>(a, c, f, x);
+  ensemble_bar<Cg1, kExt, kModel>(a, c, f, x);
 }
 
 }  // namespace
 
-// the model mode is the handle's (ViscoConst::paper), the scheduled instantiation runs when x is given
+// the model mode is the handle's (ViscoConst::paper: 0 reference, 1 paper, 2 paper with the exact
+// relaxation), the scheduled instantiation runs when x is given
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s) {
   const dim3 grid(a.nb_pad / kWave), block(kWave);
-  if (c.paper) {
-    if (x) hipLaunchKernelGGL((k_ensemble<true, true>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble<false, true>), grid, block, 0, s, a, c, f, nullptr);
+  if (c.paper == 2) {
+    if (x) hipLaunchKernelGGL((k_ensemble<true, 2>), grid, block, 0, s, a, c, f, x);
+    else hipLaunchKernelGGL((k_ensemble<false, 2>), grid, block, 0, s, a, c, f, nullptr);
+  } else if (c.paper) {
+    if (x) hipLaunchKernelGGL((k_ensemble<true, 1>), grid, block, 0, s, a, c, f, x);
+    else hipLaunchKernelGGL((k_ensemble<false, 1>), grid, block, 0, s, a, c, f, nullptr);
   } else {
-    if (x) hipLaunchKernelGGL((k_ensemble<true, false>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble<false, false>), grid, block, 0, s, a, c, f, nullptr);
+    if (x) hipLaunchKernelGGL((k_ensemble<true, 0>), grid, block, 0, s, a, c, f, x);
+    else hipLaunchKernelGGL((k_ensemble<false, 0>), grid, block, 0, s, a, c, f, nullptr);
   }
 }
 

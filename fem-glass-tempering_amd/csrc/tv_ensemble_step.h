@@ -1,7 +1,7 @@
 // The time loop of one ensemble bar, shared by the CG1 (tv_ensemble.hip) and
 // DG1 (tv_ensemble_dg.hip) temperature kernels: everything of the ensemble's
 // contract towards tv_step and the oracle that does not depend on the
-// discretisation.  A kernel is ensemble_bar<Fam, kExt, kPaper> and nothing else.
+// discretisation.  A kernel is ensemble_bar<Fam, kExt, kModel> and nothing else.
 //
 // Mapping: one lane per bar, a wave = 64 consecutive bars, one wave per
 // workgroup (so a small ensemble spreads over the CUs).  No LDS, no barriers,
@@ -25,8 +25,9 @@
 //             in the oracle), at most max_it iterations;
 //   visco     t_part of tv_visco_point.h per T dof and s_part at the sigma
 //             node that dof feeds, with its state (D = 1, stored s_tilde /
-//             sigma_tilde), then T_prev <- T.  kPaper selects the model mode
-//             of both and nothing else: in paper mode s_part also reads and
+//             sigma_tilde), then T_prev <- T.  kModel selects the model mode
+//             of both (kModel 2: s_part's exact relaxation on top of paper
+//             mode) and nothing else: in paper mode s_part also reads and
 //             rewrites s_partial / sigma_partial (ViscoFields::sp / sgp, state
 //             of a paper handle only), and the TState that t_part returns
 //             carries the dof's Tf of the previous step to the sigma node, so
@@ -72,8 +73,12 @@ __device__ __forceinline__ void set_boundary(Bar& b, double sigma_sb, double htc
 // no address pattern changes.
 // The structs come by value: by reference the scheduled CG kernel gains a
 // private segment.
-template <class Fam, bool kExt, bool kPaper>
+// kModel is ViscoConst::paper: 0 reference, 1 paper, 2 paper with the exact
+// exponential relaxation in s_part (t_part is the paper one).
+template <class Fam, bool kExt, int kModel>
 __device__ __forceinline__ void ensemble_bar(EnsArgs a, ViscoConst c, ViscoFields f, const EnsExt* __restrict__ x) {
+  static_assert(kModel >= 0 && kModel <= 2, "model id: ViscoConst::paper");
+  constexpr bool kPaper = kModel != 0;
   const int64_t bar = blockIdx.x * (int64_t)kWave + threadIdx.x;
   if (bar >= a.n_bars) return;          // tail lanes: no memory access
   if (a.failed_step[bar] != 0) return;  // frozen by an earlier failure
@@ -135,7 +140,7 @@ __device__ __forceinline__ void ensemble_bar(EnsArgs a, ViscoConst c, ViscoField
         const int64_t t = (int64_t)i * a.nb_pad + bar;
         const TState ts = t_part<false, kPaper>(c, f, t);
         const int node = Fam::sigma_node(a, i);
-        if (node >= 0) s_part<1, false, false, kPaper>(c, f, (int64_t)node * a.nb_pad + bar, ts, dirty);
+        if (node >= 0) s_part<1, false, false, kPaper, kModel == 2>(c, f, (int64_t)node * a.nb_pad + bar, ts, dirty);
         f.Tp[t] = ts.T;
       }
     }

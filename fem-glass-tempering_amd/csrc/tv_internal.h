@@ -176,7 +176,8 @@ struct ViscoConst {
   double H_over_Rg, inv_Tb, dt, half_dt, alpha_s, dalpha, inv_dim;
   double lambda_m[6], m_n[6], lambda_g[6], g_n[6], lambda_k[6], k_n[6];
   double chi;   // ViscoelasticModel.py:15 (Eq. 25, paper mode only)
-  int paper;    // model_mode: 0 reference semantics (quirks Q1-Q4 kept), 1 paper
+  int paper;    // model_mode: 0 reference semantics (quirks Q1-Q4 kept), 1 paper, 2 paper with the exact
+                // exponential relaxation (ensemble kernels only: tv_create refuses it)
 };
 
 // Pointers of the viscoelastic state (component-major, stride = n_local).
@@ -461,8 +462,8 @@ struct EnsExt {
   const int* probes;          // [n_probes] node of each probe, the same for every bar
   double* hist;               // [max_records][3 (T, Tf, sigma)][n_probes][nb_pad]
 };
-// x: device pointer, or nullptr for the plain kernel; c.paper selects the paper-mode instantiations, which
-// read and write f.sp / f.sgp (state of a paper handle) besides
+// x: device pointer, or nullptr for the plain kernel; c.paper selects the paper-mode instantiations (1, or 2
+// with the exact relaxation), which read and write f.sp / f.sgp (state of a paper handle) besides
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s);
 // DG1 temperature with CG1 stress (tv_ensemble_dg.hip, the same step driver, ensemble_bar of
 // tv_ensemble_step.h, with another family struct): the same arguments read as n_nodes mesh nodes = sigma dofs and 2 (n_nodes - 1) T dofs (2 c + l) per bar, T / Tp [2 (n_nodes - 1)][nb_pad], scr

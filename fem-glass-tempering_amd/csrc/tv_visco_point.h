@@ -18,6 +18,21 @@ __device__ __forceinline__ double taylor_E(double xi, double lam) {
   return (t0 + t1) + t2;
 }
 
+// The relaxation factor E of one Prony term and 1 - E.  EXACT = false: the
+// reference's polynomial and its subtraction.  EXACT: exp(-x) and -expm1(-x),
+// x = xi / lam (the quotient is formed twice; it is the same value).
+template <bool EXACT>
+__device__ __forceinline__ double relax_E(double xi, double lam) {
+  if constexpr (EXACT) return exp(-(xi / lam));
+  else return taylor_E(xi, lam);
+}
+
+template <bool EXACT>
+__device__ __forceinline__ double relax_omE(double xi, double lam, double E) {
+  if constexpr (EXACT) return -expm1(-(xi / lam));
+  else return 1.0 - E;
+}
+
 struct TState {
   double T, Tp, Tf, Tfo, xi;  // Tfo: Tf of the previous step (paper mode's strain)
 };
@@ -84,11 +99,16 @@ __device__ __forceinline__ TState t_part(const ViscoConst& c, const ViscoFields&
 // again.  Memory therefore always holds the exact values, in both modes.
 // PAPER: Eq. 16 feeds s~ / sigma~ from the previous s / sigma partial stresses
 // (Q3 fixed), which are then state fields (never LEAN).
-template <int D, bool ALL, bool LEAN, bool PAPER = false>
+// EXACT (paper ensembles only, opt-in): the two places where taylor_E enters
+// take the exponential itself, E = exp(-x) in Eq. 16 and 1 - E = -expm1(-x) in
+// Eq. 15 + 20, x = xi / lambda, so E lies in (0, 1] and the memory cannot grow;
+// the association of everything else is unchanged.
+template <int D, bool ALL, bool LEAN, bool PAPER = false, bool EXACT = false>
 __device__ __forceinline__ void s_part(const ViscoConst& c, const ViscoFields& f, int64_t s, const TState& ts,
                                        bool& dirty) {
   constexpr int DD = D * D;
   static_assert(!(LEAN && PAPER), "paper mode carries s / sigma partial state");
+  static_assert(PAPER || !EXACT, "the exact relaxation exists in paper mode only");
   // Eq. 9 (VEM:128-133): I*(alpha_s (T - T_prev) + (alpha_l - alpha_s)(Tf - Tf_prev)), Tf_prev == Tf (Q2)
   const double scal = c.alpha_s * (ts.T - ts.Tp) + c.dalpha * (ts.Tf - ts.Tfo);
   double tot[DD];
@@ -119,10 +139,10 @@ __device__ __forceinline__ void s_part(const ViscoConst& c, const ViscoFields& f
   double sig[DD];
   uint64_t tz = 0;  // LEAN: bits of every 0 * E product
   auto term = [&](const int n) {
-    const double Eg = taylor_E(xi, c.lambda_g[n]);
-    const double Ek = taylor_E(xi, c.lambda_k[n]);
+    const double Eg = relax_E<EXACT>(xi, c.lambda_g[n]);
+    const double Ek = relax_E<EXACT>(xi, c.lambda_k[n]);
     const double twog = 2.0 * c.g_n[n];
-    const double omEg = 1.0 - Eg, omEk = 1.0 - Ek;
+    const double omEg = relax_omE<EXACT>(xi, c.lambda_g[n], Eg), omEk = relax_omE<EXACT>(xi, c.lambda_k[n], Ek);
 #pragma unroll
     for (int q = 0; q < DD; ++q) {
       const int i = q / D, j = q % D;

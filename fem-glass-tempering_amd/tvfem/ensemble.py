@@ -56,8 +56,24 @@ main.py's parameters and dt = 0.1 (smallest ``lambda_k`` 5.0e-5) a bar at
 ``T_0 = 800 K`` stays inside the limit (``xi`` peaks at 7.0e-5) and is stable
 over 500 steps, while at 873 K ``xi`` is about 0.2 and sigma passes 1e23 after
 five steps and reaches +-inf within 100.  That is the model as the reference
-states it, not a defect of the kernel; a sweep over ``T_0`` must stay below the
-limit.  Such a bar harms no other bar of the ensemble.
+states it, not a defect of the kernel; with ``relaxation="taylor"`` (the
+default) a sweep over ``T_0`` must stay below the limit.  Such a bar harms no
+other bar of the ensemble.
+
+``model_mode="paper", relaxation="exact"`` replaces the polynomial in the two
+places it enters the stress update: ``E = exp(-x)`` multiplies the stress memory
+(Eq. 16) and ``1 - E = -expm1(-x)`` scales the increment (Eq. 15 + 20).  ``E``
+lies in (0, 1], so the memory cannot grow and a sweep may start above ``Tb``
+(all ten test bars, up to 920 K, stay finite over 500 steps with surface sigma
+0.02-0.21).  It also keeps the digits of ``1 - E`` for small ``x``: the Taylor
+form subtracts and is exactly 0 once ``x < 1e-16`` (below roughly 575-650 K), so
+with it the cold, elastic part of a quench adds no stress and the residual
+stress is low by tens of percent even inside the limit.  Nothing else changes:
+T, Tf, phi, xi, the Newton counts, the failure contract, schedules, histories
+and the state fields are those of a paper ensemble; only ``sigma`` and the four
+partial-stress fields differ.  ``relaxation="exact"`` with
+``model_mode="reference"`` raises ``ValueError``; ``ens.relaxation`` holds the
+choice.  The single-problem path (``ThermoViscoProblem``) has no exact mode.
 """
 from __future__ import annotations
 
@@ -110,7 +126,7 @@ def _parse_stages(schedule):
 class ThermoViscoEnsemble:
     def __init__(self, meshes, time: tuple, dt: float, config: dict, model_parameters: dict, *,
                  n_bars: int | None = None, device: int = 0, model_mode: str = "reference",
-                 newton_rtol: float | None = None, newton_atol: float | None = None,
+                 relaxation: str = "taylor", newton_rtol: float | None = None, newton_atol: float | None = None,
                  newton_max_it: int | None = None, error_on_nonconvergence: bool = True,
                  schedule=None, history: dict | None = None) -> None:
         self._ens = None
@@ -148,6 +164,12 @@ class ThermoViscoEnsemble:
             raise ValueError("an ensemble has at least one bar")
         if model_mode not in ("reference", "paper"):
             raise ValueError("model_mode must be 'reference' or 'paper'")
+        if relaxation not in ("taylor", "exact"):
+            raise ValueError("relaxation must be 'taylor' (the reference's degree-2 polynomial) or 'exact'")
+        if relaxation == "exact" and model_mode != "paper":
+            raise ValueError("relaxation='exact' needs model_mode='paper' (reference mode is the reference's "
+                             "code, its Taylor exponential included)")
+        self.relaxation = relaxation
         self.dt = dt
         self.time = time
         self.t = self.time[0]
@@ -181,7 +203,10 @@ class ThermoViscoEnsemble:
                         _FAMILIES[config["sigma"]["element"]], int(config["sigma"]["degree"]))
         params = N.default_params(mp, dt)
         opts = N.default_options()
-        opts.model_mode = N.TV_MODEL_PAPER if model_mode == "paper" else N.TV_MODEL_REFERENCE
+        if model_mode == "paper":
+            opts.model_mode = N.TV_MODEL_PAPER_EXACT if relaxation == "exact" else N.TV_MODEL_PAPER
+        else:
+            opts.model_mode = N.TV_MODEL_REFERENCE
         if newton_rtol is not None:
             opts.newton_rtol = newton_rtol
         if newton_atol is not None:

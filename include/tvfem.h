@@ -170,7 +170,8 @@ typedef struct {
   int materialize;        /* 0: state fields only, 1: every reference field  */
   int pcg_batch;          /* iterations launched between convergence polls  */
   int pcg_variant;        /* TV_PCG_AUTO / TV_PCG_KSPCG / TV_PCG_SINGLE_REDUCTION */
-  int model_mode;         /* TV_MODEL_REFERENCE (default) / TV_MODEL_PAPER       */
+  int model_mode;         /* TV_MODEL_REFERENCE (default) / TV_MODEL_PAPER /
+                             TV_MODEL_PAPER_EXACT (ensembles only)               */
   int preconditioner;     /* TV_PC_JACOBI (default) / TV_PC_GMG (box meshes) /
                              TV_PC_AMG (unstructured meshes, one partition)      */
   int mg_levels;          /* GMG: levels incl. the fine one (0: automatic)       */
@@ -236,9 +237,15 @@ typedef struct {
  * thermal strain (ThermoViscoProblem.py:481 vs :492), xi takes the trapezoidal
  * "+" (ViscoelasticModel.py:171), s~ / sigma~ are fed from the previous s /
  * sigma partial stresses (Eq. 16, ViscoelasticModel.py:195-209), and a
- * Dirichlet condition can be applied (tv_set_dirichlet). */
+ * Dirichlet condition can be applied (tv_set_dirichlet).
+ * PAPER_EXACT (ensembles only: tv_ensemble_create_paper; every other
+ * constructor returns TV_ERR_ARG) is PAPER with the exponential relaxation
+ * itself where both other modes keep the reference's degree-2 Taylor
+ * polynomial: E = exp(-x) multiplies the stress memory (Eq. 16) and
+ * 1 - E = -expm1(-x) scales the increment (Eq. 15 + 20), x = xi / lambda. */
 #define TV_MODEL_REFERENCE 0
 #define TV_MODEL_PAPER 1
+#define TV_MODEL_PAPER_EXACT 2
 
 /* Krylov iteration form (same Jacobi-PCG iterates in exact arithmetic):
  *   KSPCG             PETSc KSPSolve_CG as written: two reductions per iteration
@@ -464,7 +471,14 @@ int tv_ensemble_create_dg(const tv_ensemble_desc* desc, const tv_fe_config* fe, 
  * multiplied by E every step: with main.py's parameters and dt = 0.1 (smallest
  * lambda_k 5.0e-5) a bar at T_0 = 800 K stays inside the limit (xi <= 7.0e-5),
  * one at 873 K (xi ~ 0.2) overflows to +-inf within 100 steps.  That is the
- * model as the reference states it; such a bar harms no other lane. */
+ * model as the reference states it; such a bar harms no other lane.
+ * model_mode == TV_MODEL_PAPER_EXACT is accepted here too (any other value is
+ * TV_ERR_ARG): the same handle, fields and contracts, with E = exp(-x) and
+ * 1 - E = -expm1(-x) in the stress update.  E lies in (0, 1], so the memory
+ * cannot grow and no T_0 limit applies; and 1 - E keeps its digits for small
+ * x, where the Taylor form's subtraction loses them (it is exactly 0 once
+ * x < 1e-16, so the cold part of a quench adds no stress in PAPER mode).
+ * Only sigma and the four partial-stress fields differ from a PAPER handle's. */
 int tv_ensemble_create_paper(const tv_ensemble_desc* desc, const tv_fe_config* fe, const tv_params* shared,
                              const tv_options* opts, int device, void** ens_out);
 int tv_ensemble_destroy(void* ens);

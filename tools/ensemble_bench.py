@@ -74,6 +74,20 @@ written partial stresses per node:
 
 The ratios are recorded, not judged; the 64x floor at 4096 bars against the
 paper-mode sequential path holds, and the tool exits non-zero below it.
+
+--exact measures the exact exponential relaxation (model_mode="paper",
+relaxation="exact", the kModel = 2 instantiations; default output
+profiles/ensemble_exact_bench.json, one key per pairing), CG1 / CG1 or with --dg
+DG1 / CG1: the setup of --paper except T_0 = 873 K, above Tb, where the Taylor
+form overflows.  In one run the exact ensemble, the same ensemble with
+relaxation="taylor" (its stress overflows at this T_0; the thermal problem and
+the Newton counts do not see it, and only its time is used) and --seq-bars
+(default 1) paper-mode bars through ThermoViscoProblem(model_mode="paper"),
+which has no exact mode: that side runs at main.py's T_0 = 800 K, inside the
+Taylor limit, so that it stays finite over all the steps.  The relaxation moves
+no byte; per Prony term two exp and two expm1 calls take the place of two
+short polynomials.  The exact / taylor time ratio is recorded,
+not judged; the 64x floor at 4096 bars holds, and the tool exits non-zero below.
 """
 import argparse
 import json
@@ -142,6 +156,25 @@ PAPER_DG_KERNEL_RECORD = {
                                 "occupancy_waves_per_simd": 2},
 }
 
+EXACT_T_0 = 873.0  # above Tb = 869 K, where glass is tempered from: outside the Taylor limit
+# the kModel = 2 (exact relaxation) instantiations, obtained the same way
+EXACT_KERNEL_RECORD = {
+    "plain_instantiation": {"vgpr_count": 235, "sgpr_spill_count": 73, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                            "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 239, "sgpr_spill_count": 135, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
+                                "occupancy_waves_per_simd": 2},
+}
+EXACT_DG_KERNEL_RECORD = {
+    "plain_instantiation": {"vgpr_count": 241, "sgpr_spill_count": 92, "vgpr_spill_count": 0,
+                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
+                            "occupancy_waves_per_simd": 2},
+    "scheduled_instantiation": {"vgpr_count": 245, "sgpr_spill_count": 117, "vgpr_spill_count": 0,
+                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
+                                "occupancy_waves_per_simd": 2},
+}
+
 
 def _time_ensembles(make, sizes, steps, reps):
     """Median / min / max wall time of solve(steps) over `reps` fresh ensembles per size, after a warm-up."""
@@ -165,11 +198,15 @@ def _time_ensembles(make, sizes, steps, reps):
     return rows
 
 
-def _time_sequential(mesh, span, cfg, n, steps, **problem_kw):
+def _time_sequential(mesh, span, cfg, n, steps, params=None, **problem_kw):
     """`n` bars one after another through ThermoViscoProblem, htc spread as in the ensembles, one context per
-    bar, after a warm-up: (the time loops alone, the same with context creation and setup)."""
-    from main import model_params
+    bar, after a warm-up: (the time loops alone, the same with context creation and setup).  `params`
+    replaces main.py's model parameters."""
     from tvfem.problem import ThermoViscoProblem
+    if params is None:
+        from main import model_params
+    else:
+        model_params = params
 
     def single(htc, steps):
         prob = ThermoViscoProblem(mesh, span, 0.1, cfg, dict(model_params, htc=float(htc)), verbose=False,
@@ -422,6 +459,100 @@ def paper_bench(args):
         sys.exit(f"paper ensemble below the {FLOOR:g}x floor at 4096 bars")
 
 
+def exact_bench(args):
+    from geometry import graded_bar
+    from main import model_params
+    from tvfem import ThermoViscoEnsemble
+
+    mesh = graded_bar()
+    n_nodes = mesh.num_vertices
+    n_cells = n_nodes - 1
+    span = (0.0, args.steps * 0.1)
+    cfg = CFG_DG if args.dg else CFG
+    families = "DG1/CG1" if args.dg else "CG1/CG1"
+    hot = dict(model_params, T_0=EXACT_T_0)
+
+    def make(relaxation):
+        def ensemble(n_bars):
+            ens = ThermoViscoEnsemble(mesh, span, 0.1, cfg, dict(hot, htc=np.linspace(50.0, 1000.0, n_bars)),
+                                      model_mode="paper", relaxation=relaxation)
+            ens.setup()
+            return ens
+        return ensemble
+
+    # a last look at the state the timed kernel leaves: finite in exact mode at this T_0
+    probe = make("exact")(64)
+    probe.solve(args.steps)
+    sigma = probe.get_field("sigma")
+    probe.close()
+    if not np.all(np.isfinite(sigma)):
+        sys.exit("exact relaxation: sigma is not finite")
+    ex = _time_ensembles(make("exact"), args.sizes, args.steps, args.reps)
+    ta = _time_ensembles(make("taylor"), args.sizes, args.steps, args.reps)
+    rows = []
+    for e, t in zip(ex, ta):
+        bar_steps = e["n_bars"] * args.steps
+        its = e["newton_its_per_step"]
+        if args.dg:  # the bytes of paper mode: the relaxation moves none
+            per_bar_step = (n_cells * DG_BYTES_CELL_NEWTON * its + 2 * n_cells * PAPER_DG_BYTES_TDOF_STEP
+                            + n_nodes * PAPER_DG_BYTES_NODE_STEP)
+        else:
+            per_bar_step = n_nodes * (BYTES_NODE_NEWTON * its + PAPER_BYTES_NODE_STEP)
+        nbytes = bar_steps * per_bar_step
+        row = dict(e, bar_steps_per_s=bar_steps / e["wall_s"], algorithmic_bytes=nbytes,
+                   hbm_fraction_of_8TBps=nbytes / e["wall_s"] / HBM_PEAK,
+                   taylor_ensemble=dict(t, bar_steps_per_s=bar_steps / t["wall_s"]),
+                   exact_over_taylor_time=e["wall_s"] / t["wall_s"])
+        rows.append(row)
+        print(f"exact {families} ensemble {e['n_bars']:6d} bars: {e['wall_s'] * 1e3:9.2f} ms  "
+              f"{row['bar_steps_per_s']:12.4g} bar-steps/s  {its:.2f} its/step  "
+              f"{row['hbm_fraction_of_8TBps']:.2%} of HBM peak;  taylor {t['wall_s'] * 1e3:9.2f} ms  "
+              f"time ratio {row['exact_over_taylor_time']:.3f}", flush=True)
+
+    # the single-problem path has no exact mode: one Taylor paper-mode bar, at main.py's T_0 = 800 K so that it
+    # stays finite over all the steps
+    seq_wall, _ = _time_sequential(mesh, span, cfg, args.seq_bars, args.steps, model_mode="paper")
+    seq_rate = args.seq_bars * args.steps / seq_wall
+    print(f"sequential {args.seq_bars} paper-mode {families} bar(s) at T_0 = {model_params['T_0']:g} K: "
+          f"{seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
+    for r in rows:
+        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
+    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "n_cells": n_cells, "steps": args.steps,
+                        "dt": 0.1, "htc": "linspace(50, 1000, n_bars)", "T_0": EXACT_T_0, "families": families,
+                        "model_mode": "paper", "relaxation": "exact", "reps": args.reps,
+                        "taylor_ensemble": "the same ensemble with relaxation=taylor, same process; at this T_0 its "
+                                           "stress overflows (the thermal problem and the Newton counts are the "
+                                           "same), so only its time is used",
+                        "sigma_abs_max_exact_64_bars": float(np.abs(sigma).max())},
+           "bytes_model": "paper mode's (tools/ensemble_bench.py --paper): the relaxation moves no byte",
+           "kernel": EXACT_DG_KERNEL_RECORD if args.dg else EXACT_KERNEL_RECORD, "ensemble": rows,
+           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
+                          "T_0": model_params["T_0"],
+                          "timed": f"ThermoViscoProblem {families} model_mode=paper (Taylor; no exact mode exists "
+                                   f"there) at T_0 = {model_params['T_0']:g} K, inside the Taylor limit, all "
+                                   f"{args.steps} steps: solve() and a final field read per bar; context creation "
+                                   "and setup left out"},
+           "floor_ratio_at_4096": FLOOR}
+    at = [r for r in rows if r["n_bars"] == 4096]
+    if at:
+        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
+        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
+    # one file for both pairings, keyed by the families: a run replaces its own key and keeps the other
+    out = args.out or os.path.join(ROOT, "profiles", "ensemble_exact_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    both = {}
+    if os.path.exists(out):
+        with open(out) as fh:
+            both = json.load(fh)
+    both[families] = res
+    with open(out, "w") as fh:
+        json.dump(both, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print(json.dumps({"out": out, "ratio_at_4096": res.get("ratio_at_4096")}))
+    if at and res["ratio_at_4096"] < FLOOR:
+        sys.exit(f"exact ensemble below the {FLOOR:g}x floor at 4096 bars")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--sizes", type=int, nargs="+", default=[64, 1024, 4096, 16384])
@@ -440,9 +571,14 @@ def main():
     ap.add_argument("--paper", action="store_true",
                     help="the paper-mode ensemble (with --dg: DG1 / CG1) against the reference-mode ensemble and "
                          "its own sequential path")
+    ap.add_argument("--exact", action="store_true",
+                    help="the exact-relaxation paper ensemble (with --dg: DG1 / CG1) at T_0 = 873 K against the "
+                         "paper-mode ensemble and one sequential paper-mode bar")
     args = ap.parse_args()
     if args.seq_bars is None:
-        args.seq_bars = 1 if args.paper else 4
+        args.seq_bars = 1 if args.paper or args.exact else 4
+    if args.exact:
+        return exact_bench(args)
     if args.paper:
         return paper_bench(args)
     if args.scheduled:
