@@ -258,22 +258,7 @@ int ens_create(const char* fn, bool dg, bool paper, const tv_ensemble_desc* d, c
   c->x.every = 1;
   c->par.resize((size_t)3 * nb);
   for (int q = 0; q < 3; ++q) std::copy_n(par.begin() + (size_t)q * pad, nb, c->par.begin() + (size_t)q * nb);
-  // the shared viscoelastic constants, as visco_setup (tv_solver.cpp) forms them
-  ViscoConst& k = c->vc;
-  k.H_over_Rg = P->H / P->Rg;
-  k.inv_Tb = 1.0 / P->Tb;
-  k.dt = P->dt;
-  k.half_dt = P->dt / 2;
-  k.alpha_s = P->alpha_solid;
-  k.dalpha = P->alpha_liquid - P->alpha_solid;
-  k.inv_dim = 1.0;
-  k.chi = 0.5;
-  k.paper = exact ? 2 : (paper ? 1 : 0);  // the kernels' model id
-  for (int i = 0; i < 6; ++i) {
-    k.lambda_m[i] = P->lambda_m[i]; k.m_n[i] = P->m_n[i];
-    k.lambda_g[i] = P->lambda_g[i]; k.g_n[i] = P->g_n[i];
-    k.lambda_k[i] = P->lambda_k[i]; k.k_n[i] = P->k_n[i];
-  }
+  fill_visco_const(c->vc, *P, 1, exact ? 2 : (paper ? 1 : 0));  // the kernels' model id
   ViscoFields& v = c->vf;
   std::memset(&v, 0, sizeof(v));
   v.sT = (int64_t)nT * pad;

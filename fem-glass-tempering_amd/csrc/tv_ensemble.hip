@@ -143,16 +143,9 @@ __global__ __launch_bounds__(kWave) void k_ensemble(EnsArgs a, ViscoConst c, Vis
 // relaxation), the scheduled instantiation runs when x is given
 void launch_ensemble(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s) {
   const dim3 grid(a.nb_pad / kWave), block(kWave);
-  if (c.paper == 2) {
-    if (x) hipLaunchKernelGGL((k_ensemble<true, 2>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble<false, 2>), grid, block, 0, s, a, c, f, nullptr);
-  } else if (c.paper) {
-    if (x) hipLaunchKernelGGL((k_ensemble<true, 1>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble<false, 1>), grid, block, 0, s, a, c, f, nullptr);
-  } else {
-    if (x) hipLaunchKernelGGL((k_ensemble<true, 0>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble<false, 0>), grid, block, 0, s, a, c, f, nullptr);
-  }
+  dispatch_ensemble(c.paper, x != nullptr, [&](auto ext, auto model) {
+    hipLaunchKernelGGL((k_ensemble<decltype(ext)::value, decltype(model)::value>), grid, block, 0, s, a, c, f, x);
+  });
 }
 
 }  // namespace tv

@@ -218,16 +218,9 @@ __global__ __launch_bounds__(kWave) void k_ensemble_dg(EnsArgs a, ViscoConst c, 
 // relaxation), the scheduled instantiation runs when x is given
 void launch_ensemble_dg(const EnsArgs& a, const ViscoConst& c, const ViscoFields& f, const EnsExt* x, hipStream_t s) {
   const dim3 grid(a.nb_pad / kWave), block(kWave);
-  if (c.paper == 2) {
-    if (x) hipLaunchKernelGGL((k_ensemble_dg<true, 2>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble_dg<false, 2>), grid, block, 0, s, a, c, f, nullptr);
-  } else if (c.paper) {
-    if (x) hipLaunchKernelGGL((k_ensemble_dg<true, 1>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble_dg<false, 1>), grid, block, 0, s, a, c, f, nullptr);
-  } else {
-    if (x) hipLaunchKernelGGL((k_ensemble_dg<true, 0>), grid, block, 0, s, a, c, f, x);
-    else hipLaunchKernelGGL((k_ensemble_dg<false, 0>), grid, block, 0, s, a, c, f, nullptr);
-  }
+  dispatch_ensemble(c.paper, x != nullptr, [&](auto ext, auto model) {
+    hipLaunchKernelGGL((k_ensemble_dg<decltype(ext)::value, decltype(model)::value>), grid, block, 0, s, a, c, f, x);
+  });
 }
 
 }  // namespace tv

@@ -165,4 +165,14 @@ __device__ __forceinline__ void ensemble_bar(EnsArgs a, ViscoConst c, ViscoField
   if (failed) a.failed_step[bar] = failed;
 }
 
+// The run-time pair of a launch (the handle's model id ViscoConst::paper, whether an EnsExt is given) as
+// ensemble_bar's compile-time pair: fn(integral_constant<bool, kExt>, integral_constant<int, kModel>).
+template <class Fn>
+inline void dispatch_ensemble(int model, bool ext, Fn&& fn) {
+  auto with_model = [&](auto m) { ext ? fn(std::true_type{}, m) : fn(std::false_type{}, m); };
+  if (model == 2) with_model(std::integral_constant<int, 2>{});
+  else if (model) with_model(std::integral_constant<int, 1>{});
+  else with_model(std::integral_constant<int, 0>{});
+}
+
 }  // namespace tv

@@ -179,6 +179,8 @@ struct ViscoConst {
   int paper;    // model_mode: 0 reference semantics (quirks Q1-Q4 kept), 1 paper, 2 paper with the exact
                 // exponential relaxation (ensemble kernels only: tv_create refuses it)
 };
+// every ViscoConst is filled here: `model` becomes `paper`, inv_dim is 1.0 / dim (an ensemble bar: dim 1)
+void fill_visco_const(ViscoConst& k, const tv_params& P, int dim, int model);
 
 // Pointers of the viscoelastic state (component-major, stride = n_local).
 // the incremental Newton test of newton(), decided ONCE on the device

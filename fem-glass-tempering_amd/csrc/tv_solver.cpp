@@ -586,22 +586,25 @@ int visco_timing_flush(Ctx* c) {
   return TV_OK;
 }
 
-void visco_setup(Ctx* c, ViscoConst& k, ViscoFields& v) {
-  const tv_params& P = c->P;
+void fill_visco_const(ViscoConst& k, const tv_params& P, int dim, int model) {
   k.H_over_Rg = P.H / P.Rg;
   k.inv_Tb = 1.0 / P.Tb;
   k.dt = P.dt;
   k.half_dt = P.dt / 2;
   k.alpha_s = P.alpha_solid;
   k.dalpha = P.alpha_liquid - P.alpha_solid;
-  k.inv_dim = 1.0 / c->dim;
+  k.inv_dim = 1.0 / dim;
   k.chi = 0.5;  // ViscoelasticModel.py:15
-  k.paper = (c->O.model_mode == TV_MODEL_PAPER) ? 1 : 0;
+  k.paper = model;
   for (int i = 0; i < 6; ++i) {
     k.lambda_m[i] = P.lambda_m[i]; k.m_n[i] = P.m_n[i];
     k.lambda_g[i] = P.lambda_g[i]; k.g_n[i] = P.g_n[i];
     k.lambda_k[i] = P.lambda_k[i]; k.k_n[i] = P.k_n[i];
   }
+}
+
+void visco_setup(Ctx* c, ViscoConst& k, ViscoFields& v) {
+  fill_visco_const(k, c->P, c->dim, (c->O.model_mode == TV_MODEL_PAPER) ? 1 : 0);
   std::memset(&v, 0, sizeof(v));
   v.sT = field_stride(c, 0);
   v.sS = field_stride(c, 1);

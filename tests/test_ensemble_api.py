@@ -1,58 +1,26 @@
 """The ensemble surface without a GPU: the ABI additions exist, every refusal of
 tv_ensemble_create is decided before the GPU is touched, and the Python class
 validates its arguments before it creates anything."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from ensemble_api_util import CFG_CG as CFG, create, header, load_lib, no_gpu_env
 from oracle.tv_oracle import MAIN_MODEL_PARAMS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "fem-glass-tempering_amd")
-CFG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
 ENSEMBLE_SYMBOLS = ["tv_ensemble_create", "tv_ensemble_destroy", "tv_ensemble_set_initial_condition",
                     "tv_ensemble_step", "tv_ensemble_get_field", "tv_ensemble_set_field", "tv_ensemble_stats"]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(PKG, "tvfem", "libtvfem.so")
-    if not os.path.exists(so):
-        subprocess.run(["make", "-C", PKG, "-j8"], check=True, capture_output=True)
-    from tvfem import _native as N
-    return N.load_library()
-
-
-def _create(lib, n_bars=3, n_cells=4, coords=None, fe=None, model_mode=None):
-    from tvfem import _native as N
-    if coords is None:
-        coords = np.tile(np.linspace(0.0, 1.0, max(n_cells, 0) + 1), (max(n_bars, 1), 1))
-    coords = np.ascontiguousarray(coords, dtype=np.float64)
-    desc = N.EnsembleDesc()
-    desc.n_bars, desc.n_cells = n_bars, n_cells
-    desc.coords = coords.ctypes.data_as(C.POINTER(C.c_double))
-    fe = fe or N.FeConfig(N.TV_CG, 1, N.TV_CG, 1)
-    params = N.default_params(None, 0.1)
-    opts = N.default_options()
-    if model_mode is not None:
-        opts.model_mode = model_mode
-    ens = C.c_void_p()
-    rc = lib.tv_ensemble_create(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), 0, C.byref(ens))
-    msg = (lib.tv_last_error(None) or b"").decode()
-    if rc == N.TV_OK:
-        lib.tv_ensemble_destroy(ens)
-    return rc, msg
+    return load_lib()
 
 
 def test_abi_additions_present(lib):
     from tvfem import _native as N
-    header = open(os.path.join(ROOT, "include", "tvfem.h")).read()
-    assert "tv_ensemble_desc" in header
+    assert "tv_ensemble_desc" in header()
     for name in ENSEMBLE_SYMBOLS:
-        assert name in header and name in N.EXPORTS and hasattr(lib, name), name
+        assert name in header() and name in N.EXPORTS and hasattr(lib, name), name
     assert lib.tv_abi_version() == 8  # additive: nothing existing moved
 
 
@@ -67,9 +35,8 @@ def test_abi_additions_present(lib):
 def test_create_refuses_before_the_gpu(lib, case, kw, word):
     from tvfem import _native as N
     if "fe" in kw:
-        fam = {"CG": N.TV_CG, "DG": N.TV_DG}
-        kw = dict(kw, fe=N.FeConfig(fam[kw["fe"][0]], 1, fam[kw["fe"][1]], 1))
-    rc, msg = _create(lib, **kw)
+        kw = dict(kw, fe=(kw["fe"][0], 1, kw["fe"][1], 1))
+    rc, msg = create(lib, "tv_ensemble_create", **kw)
     assert rc == N.TV_ERR_ARG, (case, rc, msg)
     assert word in msg, (case, msg)
     if case.startswith("non-increasing"):
@@ -77,14 +44,9 @@ def test_create_refuses_before_the_gpu(lib, case, kw, word):
 
 
 def test_create_without_gpu_fails_loudly(lib):
-    try:
-        import torch
-        if torch.cuda.is_available():
-            pytest.skip("GPU present")
-    except Exception:
-        pass
+    no_gpu_env()
     from tvfem import _native as N
-    rc, msg = _create(lib)
+    rc, msg = create(lib, "tv_ensemble_create")
     assert rc == N.TV_ERR_HIP
     assert "GPU" in msg or "HIP" in msg
 

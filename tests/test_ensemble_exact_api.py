@@ -4,76 +4,36 @@ and refuses any other value, every other constructor refuses it before the GPU i
 touched, and the Python class validates relaxation= and routes "exact" to the native
 constructor."""
 import ctypes as C
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
+from ensemble_api_util import CFG_CG, CFG_DG, CG1_CG1, DG1_CG1, create, header, load_lib, no_gpu_env
 from oracle.tv_oracle import MAIN_MODEL_PARAMS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "fem-glass-tempering_amd")
-CFG_CG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
-CFG_DG = {"T": {"element": "DG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
 EXACT = 2
-CG1_CG1 = ("CG", 1, "CG", 1)
-DG1_CG1 = ("DG", 1, "CG", 1)
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(PKG, "tvfem", "libtvfem.so")
-    if not os.path.exists(so):
-        subprocess.run(["make", "-C", PKG, "-j8"], check=True, capture_output=True)
-    from tvfem import _native as N
-    return N.load_library()
-
-
-def _no_gpu():
-    try:
-        import torch
-        if torch.cuda.is_available():
-            pytest.skip("GPU present")
-    except ImportError:
-        pass
-
-
-def _create(lib, fn, fe=CG1_CG1, model_mode=EXACT):
-    from tvfem import _native as N
-    coords = np.ascontiguousarray(np.tile(np.linspace(0.0, 1.0, 5), (3, 1)))
-    desc = N.EnsembleDesc()
-    desc.n_bars, desc.n_cells = 3, 4
-    desc.coords = coords.ctypes.data_as(C.POINTER(C.c_double))
-    fam = {"CG": N.TV_CG, "DG": N.TV_DG}
-    fe = N.FeConfig(fam[fe[0]], fe[1], fam[fe[2]], fe[3])
-    params = N.default_params(None, 0.1)
-    opts = N.default_options()
-    opts.model_mode = model_mode
-    ens = C.c_void_p()
-    rc = getattr(lib, fn)(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), 0, C.byref(ens))
-    msg = (lib.tv_last_error(None) or b"").decode()
-    if rc == N.TV_OK:
-        lib.tv_ensemble_destroy(ens)
-    return rc, msg
+    return load_lib()
 
 
 def test_constant_present(lib):
     from tvfem import _native as N
-    header = open(os.path.join(ROOT, "include", "tvfem.h")).read()
-    assert re.search(r"^#define TV_MODEL_PAPER_EXACT 2\s*$", header, re.M)
+    assert re.search(r"^#define TV_MODEL_PAPER_EXACT 2\s*$", header(), re.M)
     assert N.TV_MODEL_PAPER_EXACT == EXACT
     assert (N.TV_MODEL_REFERENCE, N.TV_MODEL_PAPER) == (0, 1)
-    assert re.search(r"^#define TV_ABI_VERSION 8\b", header, re.M)
+    assert re.search(r"^#define TV_ABI_VERSION 8\b", header(), re.M)
     assert lib.tv_abi_version() == 8 and N.ABI_VERSION == 8  # additive: nothing existing moved
 
 
 @pytest.mark.parametrize("fe", [CG1_CG1, DG1_CG1])
 def test_create_paper_accepts_exact_as_far_as_the_device(lib, fe):
-    _no_gpu()
+    no_gpu_env()
     from tvfem import _native as N
-    rc, msg = _create(lib, "tv_ensemble_create_paper", fe=fe)
+    rc, msg = create(lib, "tv_ensemble_create_paper", fe=fe, model_mode=EXACT)
     assert rc == N.TV_ERR_HIP, (rc, msg)
     assert "GPU" in msg or "HIP" in msg
 
@@ -82,7 +42,7 @@ def test_create_paper_accepts_exact_as_far_as_the_device(lib, fe):
 @pytest.mark.parametrize("model_mode", [3, -1, 7])
 def test_create_paper_refuses_any_other_value(lib, fe, model_mode):
     from tvfem import _native as N
-    rc, msg = _create(lib, "tv_ensemble_create_paper", fe=fe, model_mode=model_mode)
+    rc, msg = create(lib, "tv_ensemble_create_paper", fe=fe, model_mode=model_mode)
     assert rc == N.TV_ERR_ARG, (rc, msg)
     assert msg.startswith("tv_ensemble_create_paper: ") and "model_mode" in msg, msg
 
@@ -91,7 +51,7 @@ def test_create_paper_refuses_any_other_value(lib, fe, model_mode):
 def test_reference_constructors_refuse_exact(lib, fn, fe):
     """TV_ERR_ARG also where a GPU is present: decided before the first HIP call."""
     from tvfem import _native as N
-    rc, msg = _create(lib, fn, fe=fe)
+    rc, msg = create(lib, fn, fe=fe, model_mode=EXACT)
     assert rc == N.TV_ERR_ARG, (rc, msg)
     assert msg.startswith(fn + ": ") and "model_mode" in msg, msg
 
@@ -165,7 +125,7 @@ def test_class_routes_exact_to_the_native_constructor(lib, cfg, monkeypatch):
                                 relaxation=relaxation)
         assert seen[-1] == want
     monkeypatch.undo()
-    _no_gpu()
+    no_gpu_env()
     with pytest.raises(NativeError) as exc:
         ThermoViscoEnsemble(interval_mesh(50.0, 10), (0, 1), 0.1, cfg, mp, model_mode="paper", relaxation="exact",
                             history=dict(nodes=[0, 5, 10], every=2))

@@ -4,66 +4,24 @@ of the reference mode, every other refusal is that of the family's constructor
 and is decided before the GPU is touched, and the Python class routes
 model_mode="paper" to it for either config."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from ensemble_api_util import CFG_CG, CFG_DG, DG1_CG1, create, header, load_lib, no_gpu_env
 from oracle.tv_oracle import MAIN_MODEL_PARAMS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "fem-glass-tempering_amd")
-CFG_CG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
-CFG_DG = {"T": {"element": "DG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
 PAPER = 1
-DG1_CG1 = ("DG", 1, "CG", 1)
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(PKG, "tvfem", "libtvfem.so")
-    if not os.path.exists(so):
-        subprocess.run(["make", "-C", PKG, "-j8"], check=True, capture_output=True)
-    from tvfem import _native as N
-    return N.load_library()
-
-
-def _no_gpu():
-    try:
-        import torch
-        if torch.cuda.is_available():
-            pytest.skip("GPU present")
-    except ImportError:
-        pass
-
-
-def _create(lib, n_bars=3, n_cells=4, coords=None, fe=("CG", 1, "CG", 1), model_mode=PAPER, null_options=False):
-    from tvfem import _native as N
-    if coords is None:
-        coords = np.tile(np.linspace(0.0, 1.0, max(n_cells, 0) + 1), (max(n_bars, 1), 1))
-    coords = np.ascontiguousarray(coords, dtype=np.float64)
-    desc = N.EnsembleDesc()
-    desc.n_bars, desc.n_cells = n_bars, n_cells
-    desc.coords = coords.ctypes.data_as(C.POINTER(C.c_double))
-    fam = {"CG": N.TV_CG, "DG": N.TV_DG}
-    fe = N.FeConfig(fam[fe[0]], fe[1], fam[fe[2]], fe[3])
-    params = N.default_params(None, 0.1)
-    opts = N.default_options()
-    opts.model_mode = model_mode
-    ens = C.c_void_p()
-    rc = lib.tv_ensemble_create_paper(C.byref(desc), C.byref(fe), C.byref(params),
-                                      None if null_options else C.byref(opts), 0, C.byref(ens))
-    msg = (lib.tv_last_error(None) or b"").decode()
-    if rc == N.TV_OK:
-        lib.tv_ensemble_destroy(ens)
-    return rc, msg
+    return load_lib()
 
 
 def test_symbol_present(lib):
     from tvfem import _native as N
-    header = open(os.path.join(ROOT, "include", "tvfem.h")).read()
-    assert "tv_ensemble_create_paper" in header
+    assert "tv_ensemble_create_paper" in header()
     assert "tv_ensemble_create_paper" in N.EXPORTS
     assert hasattr(lib, "tv_ensemble_create_paper")
     assert lib.tv_abi_version() == 8  # additive: nothing existing moved
@@ -87,7 +45,7 @@ def test_symbol_present(lib):
 ])
 def test_create_paper_refuses_before_the_gpu(lib, case, kw, words):
     from tvfem import _native as N
-    rc, msg = _create(lib, **kw)
+    rc, msg = create(lib, "tv_ensemble_create_paper", **dict(dict(model_mode=PAPER), **kw))
     assert rc == N.TV_ERR_ARG, (case, rc, msg)
     assert msg.startswith("tv_ensemble_create_paper: "), (case, msg)
     for word in words:
@@ -96,9 +54,9 @@ def test_create_paper_refuses_before_the_gpu(lib, case, kw, words):
 
 @pytest.mark.parametrize("fe", [("CG", 1, "CG", 1), ("DG", 1, "CG", 1)])
 def test_create_paper_without_gpu_fails_loudly(lib, fe):
-    _no_gpu()
+    no_gpu_env()
     from tvfem import _native as N
-    rc, msg = _create(lib, fe=fe)
+    rc, msg = create(lib, "tv_ensemble_create_paper", fe=fe, model_mode=PAPER)
     assert rc == N.TV_ERR_HIP
     assert "GPU" in msg or "HIP" in msg
 
@@ -114,7 +72,7 @@ def test_null_arguments(lib):
 def test_class_routes_paper_mode_to_the_native_constructor(lib, cfg):
     """Python validation passes; what fails without a GPU is the native creation, not
     the refusal of PAPER by tv_ensemble_create / tv_ensemble_create_dg."""
-    _no_gpu()
+    no_gpu_env()
     from tvfem import NativeError, ThermoViscoEnsemble, interval_mesh
     from tvfem import _native as N
     from tvfem.ensemble import SIGMA_FAMILY, STATE_FIELDS

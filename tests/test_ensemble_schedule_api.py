@@ -2,35 +2,25 @@
 additions exist, the new entry points refuse a null handle, and the Python
 class decides every refusal of `schedule=` / `history=` before it creates
 anything (so a machine without a GPU still gets the ValueError)."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from ensemble_api_util import CFG_CG as CFG, header, load_lib
 from oracle.tv_oracle import MAIN_MODEL_PARAMS
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "fem-glass-tempering_amd")
-CFG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
 NEW_SYMBOLS = ["tv_ensemble_set_schedule", "tv_ensemble_history_open", "tv_ensemble_history_read"]
 
 
 @pytest.fixture(scope="module")
 def lib():
-    so = os.path.join(PKG, "tvfem", "libtvfem.so")
-    if not os.path.exists(so):
-        subprocess.run(["make", "-C", PKG, "-j8"], check=True, capture_output=True)
-    from tvfem import _native as N
-    return N.load_library()
+    return load_lib()
 
 
 def test_symbols_present(lib):
     from tvfem import _native as N
-    header = open(os.path.join(ROOT, "include", "tvfem.h")).read()
-    assert "tv_ensemble_schedule" in header
+    assert "tv_ensemble_schedule" in header()
     for name in NEW_SYMBOLS:
-        assert name in header and name in N.EXPORTS and hasattr(lib, name), name
+        assert name in header() and name in N.EXPORTS and hasattr(lib, name), name
     assert lib.tv_abi_version() == 8  # additive: nothing existing moved
 
 

@@ -1,9 +1,9 @@
 """tests/exact_relaxation.py: the helper that gives the unchanged CPU oracle the exact
-exponential relaxation, the reference of tests/test_ensemble_exact.py.  No GPU.
+exponential relaxation, the reference of the exact cells of tests/ensemble_cases.py.  No GPU.
 
 The helper's object against numpy on x from 1e-300 to 1e3, against the Taylor polynomial
 inside its remainder bound, the restore of the oracle's own function, and what the
-relaxation does to the model: under the patch all ten BARS of tests/test_ensemble.py, CG1 /
+relaxation does to the model: under the patch all ten BARS of tests/ensemble_cases.py, CG1 /
 CG1 and DG1 / CG1 at 16 cells, are finite in every compared field after every one of 500
 steps (measured surface sigma 0.024-0.21, 3.9e-5 on the equilibrium bar 4), while without
 it bar 5 (873 K) has a non-finite sigma within 100 steps (measured: step 48, CG).
@@ -11,7 +11,8 @@ it bar 5 (873 K) has a non-finite sigma within 100 steps (measured: step 48, CG)
 import numpy as np
 import pytest
 
-from exact_relaxation import ExactE, exact_exponential, exact_relaxation, oracle_run
+from ensemble_cases import CELL, oracle_run
+from exact_relaxation import ExactE, exact_exponential, exact_relaxation
 from oracle import tv_oracle as O
 
 
@@ -87,7 +88,7 @@ def test_original_function_is_restored():
 def test_all_ten_bars_stay_finite_over_500_steps(fam):
     original = O.taylor_exponential
     for bar in range(10):
-        ref = oracle_run(fam, bar, 16, 500)
+        ref = oracle_run(CELL[fam + "-exact"], bar, 16, 500)
         assert ref["first_nonfinite"] is None, (fam, bar, ref["first_nonfinite"])
         for name, v in ref["end"].items():
             assert np.all(np.isfinite(v)), (fam, bar, name)
@@ -98,8 +99,8 @@ def test_all_ten_bars_stay_finite_over_500_steps(fam):
 
 
 def test_taylor_bar_5_overflows_within_100_steps():
-    ref = oracle_run("cg", 5, 16, 100, False, False)
+    ref = oracle_run(CELL["cg-paper"], 5, 16, 100, finite=False)
     assert ref["first_nonfinite"] is not None and ref["first_nonfinite"] <= 100
     assert not np.all(np.isfinite(ref["end"]["sigma"]))
     # and the exact relaxation keeps the same bar finite over the same steps
-    assert oracle_run("cg", 5, 16, 100)["first_nonfinite"] is None
+    assert oracle_run(CELL["cg-exact"], 5, 16, 100)["first_nonfinite"] is None

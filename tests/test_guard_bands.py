@@ -564,45 +564,42 @@ def test_partitioned_step(name, extra):
     assert g["T_vs_single"] < 1e-12, g
 
 
-# ---- the ensemble kernel ----------------------------------------------------------------------
+# ---- the ensemble kernels ---------------------------------------------------------------------
+ENSEMBLE_STEPS_EVERY = {"reference": (20, 5), "paper": (8, 2), "exact": (8, 2)}
+
+
+def ensemble_cell(cell, n_bars, n_cells, monkeypatch):
+    """One (family, model) cell of tests/ensemble_cases.py: tail lanes (65 bars), a second wave and workgroup
+    (130); plain, then with a three-stage schedule and a history of 2 probes; every state field (nine, or
+    eleven on a paper handle), record and statistic bitwise.  Every cell is a code object of its own, a paper
+    handle has two allocations more (s_partial, sigma_partial), and n_cells = 1 is where the clamped chunk
+    indices of the two sweeps are most likely to stray.  The reference cells run 20 steps with a record every
+    5; the paper and exact cells 8 steps, over which the hot bars stay finite in paper mode, with a record
+    every 2: there no NaN is left to hide a poisoned read behind, and every compared value is asserted finite.
+    The kernels are pinned to the oracle by tests/test_ensemble*.py on these bars: (c) here is the first bar's
+    T against those runs' oracle (1e-10)."""
+    _torch()
+    from ensemble_cases import oracle_run, plain_and_scheduled
+    n_steps, every = ENSEMBLE_STEPS_EVERY[cell.model]
+    got = _twice(monkeypatch, lambda R: plain_and_scheduled(cell, n_bars, n_cells, n_steps, every, R.finish))
+    assert got["plain/T"].shape == (n_bars, cell.n_T(n_cells)) and got["plain/sigma"].shape == (n_bars, n_cells + 1)
+    if cell.paper:
+        assert got["plain/s_partial"].shape == got["plain/sigma_partial"].shape == (n_bars, 6 * (n_cells + 1))
+    assert got["hist/T"].shape == (4, n_bars, 2)
+    assert not got["plain/failed"].any() and not got["sched/failed"].any()
+    if cell.finite_sigma:
+        for k, v in got.items():
+            assert np.all(np.isfinite(v)), k
+    ref = oracle_run(cell, 0, n_cells, n_steps)
+    assert relerr(got["plain/T"][0], ref["end"]["T"]) <= 1e-10
+
+
 @pytest.mark.parametrize("n_cells", [3, 16])
 @pytest.mark.parametrize("n_bars", [1, 65, 130])
 def test_ensemble(n_bars, n_cells, monkeypatch):
-    """tv_ensemble.hip: tail lanes (65 bars), a second wave and workgroup (130); plain, then with a three-stage
-    schedule and a history of 2 probes; 20 steps; fields, history and statistics bitwise.  The kernel is pinned
-    to the oracle by tests/test_ensemble*.py on these bars: (c) here is the first bar's T against those runs'
-    oracle (1e-10)."""
-    _torch()
-    from test_ensemble import STATE as ESTATE, _ensemble, _oracle_run
-    from test_ensemble_schedule import _scheduled
-
-    def run(R):
-        out = {}
-        ens = _ensemble([b % 10 for b in range(n_bars)], n_cells)
-        ens.solve(20)
-        for f in ESTATE:
-            out["plain/" + f] = ens.get_field(f)
-        out["plain/its"] = np.asarray(ens.newton_iterations)
-        out["plain/total"] = np.asarray(ens.newton_total)
-        out["plain/failed"] = np.asarray(ens.failed_step)
-        R.finish(ens._lib)
-        ens.close()
-        ens = _scheduled([b % 6 for b in range(n_bars)], n_cells, history=dict(nodes=[0, n_cells], every=5))
-        ens.solve(20)
-        for f in ESTATE:
-            out["sched/" + f] = ens.get_field(f)
-        h = ens.get_history()
-        for k in ("step", "T", "Tf", "sigma"):
-            out["hist/" + k] = np.asarray(h[k])
-        out["sched/total"] = np.asarray(ens.newton_total)
-        R.finish(ens._lib)
-        ens.close()
-        return out
-
-    got = _twice(monkeypatch, run)
-    assert got["hist/T"].shape == (4, n_bars, 2)
-    ref = _oracle_run(0, n_cells, 20, False)
-    assert relerr(got["plain/T"][0], ref["end"]["T"]) <= 1e-10
+    """tv_ensemble.hip, the CG1 reference cell; the other five: tests/test_guard_bands_{dg,paper,exact}.py."""
+    from ensemble_cases import CELL
+    ensemble_cell(CELL["cg-reference"], n_bars, n_cells, monkeypatch)
 
 
 # ---- the instruments themselves ---------------------------------------------------------------

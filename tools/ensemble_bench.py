@@ -107,73 +107,115 @@ for p in (PKG, ROOT):
         sys.path.insert(0, p)
 
 HBM_PEAK = 8.0e12  # B/s, MI355X
-BYTES_NODE_NEWTON = 80
-BYTES_NODE_STEP = 344
 FLOOR = 64.0
-CFG = {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
-CFG_DG = {"T": {"element": "DG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
+CFGS = {"cg": {"T": {"element": "CG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}},
+        "dg": {"T": {"element": "DG", "degree": 1}, "sigma": {"element": "CG", "degree": 1}}}
+FAMILIES = {"cg": "CG1/CG1", "dg": "DG1/CG1"}
+# ThermoViscoEnsemble keywords of a model
+ENS_KW = {"reference": {}, "paper": dict(model_mode="paper"), "exact": dict(model_mode="paper", relaxation="exact")}
+# the algorithmic bytes (module docstring): CG per node, DG per cell / T dof / node; [reference, paper]
+BYTES_NODE_NEWTON = 80
+BYTES_NODE_STEP = [344, 448]
 DG_BYTES_CELL_NEWTON = 176
-DG_BYTES_TDOF_STEP = 144
-DG_BYTES_NODE_STEP = 200
-# the cross-compiler's resource report of csrc/tv_ensemble_dg.hip and csrc/tv_ensemble.hip (gfx950, the Makefile's
-# flags: -O3 -ffp-contract=off), both instantiations of csrc/tv_ensemble_step.h; DESIGN.md section 15 says how it
-# is obtained.  scratch_instructions counts scratch loads / stores in the instruction stream.
-DG_KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 236, "sgpr_spill_count": 63, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                            "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 241, "sgpr_spill_count": 73, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
-                                "occupancy_waves_per_simd": 2},
-}
-KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 234, "sgpr_spill_count": 63, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                            "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 239, "sgpr_spill_count": 77, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                                "occupancy_waves_per_simd": 2},
-}
-
-PAPER_BYTES_NODE_STEP = 448
-PAPER_DG_BYTES_TDOF_STEP = 152
-PAPER_DG_BYTES_NODE_STEP = 296
-# the kPaper instantiations, obtained the same way (tools/kres.py)
-PAPER_KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 233, "sgpr_spill_count": 82, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                            "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 237, "sgpr_spill_count": 96, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
-                                "occupancy_waves_per_simd": 2},
-}
-PAPER_DG_KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 238, "sgpr_spill_count": 61, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                            "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 243, "sgpr_spill_count": 79, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
-                                "occupancy_waves_per_simd": 2},
-}
-
+DG_BYTES_TDOF_STEP = [144, 152]
+DG_BYTES_NODE_STEP = [200, 296]
 EXACT_T_0 = 873.0  # above Tb = 869 K, where glass is tempered from: outside the Taylor limit
-# the kModel = 2 (exact relaxation) instantiations, obtained the same way
-EXACT_KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 235, "sgpr_spill_count": 73, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                            "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 239, "sgpr_spill_count": 135, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
-                                "occupancy_waves_per_simd": 2},
+
+
+def _rec(vgpr, sgpr_spill, private=0):
+    return {"vgpr_count": vgpr, "sgpr_spill_count": sgpr_spill, "vgpr_spill_count": 0,
+            "private_segment_fixed_size": private, "scratch_instructions": 0, "occupancy_waves_per_simd": 2}
+
+
+# the cross-compiler's resource report of the instantiations of csrc/tv_ensemble_step.h in csrc/tv_ensemble.hip
+# and csrc/tv_ensemble_dg.hip (gfx950, the Makefile's flags: -O3 -ffp-contract=off; tools/kres.py; DESIGN.md
+# section 15 says how it is obtained).  scratch_instructions counts scratch loads / stores in the instruction
+# stream.
+KERNEL_RECORD = {
+    ("cg", "reference", "plain"): _rec(234, 63), ("cg", "reference", "scheduled"): _rec(239, 77),
+    ("dg", "reference", "plain"): _rec(236, 63), ("dg", "reference", "scheduled"): _rec(241, 73, 20),
+    ("cg", "paper", "plain"): _rec(233, 82), ("cg", "paper", "scheduled"): _rec(237, 96, 20),
+    ("dg", "paper", "plain"): _rec(238, 61), ("dg", "paper", "scheduled"): _rec(243, 79, 20),
+    ("cg", "exact", "plain"): _rec(235, 73), ("cg", "exact", "scheduled"): _rec(239, 135, 20),
+    ("dg", "exact", "plain"): _rec(241, 92), ("dg", "exact", "scheduled"): _rec(245, 117, 20),
 }
-EXACT_DG_KERNEL_RECORD = {
-    "plain_instantiation": {"vgpr_count": 241, "sgpr_spill_count": 92, "vgpr_spill_count": 0,
-                            "private_segment_fixed_size": 0, "scratch_instructions": 0,
-                            "occupancy_waves_per_simd": 2},
-    "scheduled_instantiation": {"vgpr_count": 245, "sgpr_spill_count": 117, "vgpr_spill_count": 0,
-                                "private_segment_fixed_size": 20, "scratch_instructions": 0,
-                                "occupancy_waves_per_simd": 2},
-}
+
+
+def kernel_record(fam, model):
+    return {kind + "_instantiation": KERNEL_RECORD[fam, model, kind] for kind in ("plain", "scheduled")}
+
+
+def bytes_per_bar_step(fam, paper, its, n_nodes):
+    n_cells = n_nodes - 1
+    if fam == "dg":
+        return (n_cells * DG_BYTES_CELL_NEWTON * its + 2 * n_cells * DG_BYTES_TDOF_STEP[paper]
+                + n_nodes * DG_BYTES_NODE_STEP[paper])
+    return n_nodes * (BYTES_NODE_NEWTON * its + BYTES_NODE_STEP[paper])
+
+
+def bytes_model(fam, paper):
+    if fam == "dg":
+        d = {"per_cell_newton_iteration": DG_BYTES_CELL_NEWTON, "per_T_dof_step": DG_BYTES_TDOF_STEP[paper],
+             "per_node_step": DG_BYTES_NODE_STEP[paper]}
+        return dict(d, reference_per_T_dof_step=DG_BYTES_TDOF_STEP[0],
+                    reference_per_node_step=DG_BYTES_NODE_STEP[0]) if paper else d
+    d = {"per_node_newton_iteration": BYTES_NODE_NEWTON, "per_node_step": BYTES_NODE_STEP[paper]}
+    return dict(d, reference_per_node_step=BYTES_NODE_STEP[0]) if paper else d
+
+
+def mode_of(args):
+    """What one run measures: the cell (family, model) and the cell it is held against, the names under which
+    the comparison is written, T_0, the output file and whether it is keyed by the families, --seq-bars."""
+    fam = "dg" if args.dg else "cg"
+    timed = "solve() and a final field read per bar; context creation and setup left out"
+    if args.exact:
+        return dict(cell=(fam, "exact"), label=f"exact {FAMILIES[fam]}", baseline=(fam, "paper"),
+                    baseline_key="taylor_ensemble", baseline_label="taylor", time_ratio="exact_over_taylor_time",
+                    bytes_ratio=None, T_0=EXACT_T_0, out="ensemble_exact_bench.json", keyed=True, seq_bars=1,
+                    bytes_model="paper mode's (tools/ensemble_bench.py --paper): the relaxation moves no byte",
+                    timed="ThermoViscoProblem {families} model_mode=paper (Taylor; no exact mode exists there) at "
+                          "T_0 = {T_0:g} K, inside the Taylor limit, all {steps} steps: " + timed)
+    if args.paper:
+        return dict(cell=(fam, "paper"), label=f"paper {FAMILIES[fam]}", baseline=(fam, "reference"),
+                    baseline_key="reference_ensemble", baseline_label="reference",
+                    time_ratio="paper_over_reference_time", bytes_ratio="paper_over_reference_algorithmic_bytes",
+                    T_0=None, out="ensemble_paper_bench.json", keyed=True, seq_bars=1,
+                    bytes_model=bytes_model(fam, True),
+                    timed="ThermoViscoProblem {families} model_mode=paper: " + timed)
+    if args.dg:
+        return dict(cell=("dg", "reference"), label="DG", baseline=("cg", "reference"), baseline_key="cg_ensemble",
+                    baseline_label="CG", time_ratio="dg_over_cg_time", bytes_ratio="dg_over_cg_algorithmic_bytes",
+                    T_0=None, out="ensemble_dg_bench.json", keyed=False, seq_bars=4,
+                    bytes_model=bytes_model("dg", False), timed="ThermoViscoProblem DG1/CG1: " + timed)
+    return dict(cell=("cg", "reference"), label="", baseline=None, T_0=None, out="ensemble_bench.json", keyed=False,
+                seq_bars=4, bytes_model=bytes_model("cg", False), timed=timed)
+
+
+def _maker(mesh, span, fam, model, params):
+    """n_bars -> a set-up ensemble of the cell, htc spread over the bars."""
+    from tvfem import ThermoViscoEnsemble
+
+    def ensemble(n_bars):
+        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFGS[fam], dict(params, htc=np.linspace(50.0, 1000.0, n_bars)),
+                                  **ENS_KW[model])
+        ens.setup()
+        return ens
+    return ensemble
+
+
+def _write(out, res, key=None):
+    """res as the file `out`, or, keyed, as its entry `key`: a run replaces its own key and keeps the others."""
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if key is not None:
+        both = {}
+        if os.path.exists(out):
+            with open(out) as fh:
+                both = json.load(fh)
+        both[key] = res
+        res = both
+    with open(out, "w") as fh:
+        json.dump(res, fh, indent=1, sort_keys=key is not None)
+        fh.write("\n")
 
 
 def _time_ensembles(make, sizes, steps, reps):
@@ -233,11 +275,8 @@ def scheduled_bench(args):
     mesh = graded_bar()
     n_nodes = mesh.num_vertices
     span = (0.0, args.steps * 0.1)
-
-    def plain(n_bars):
-        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFG, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)))
-        ens.setup()
-        return ens
+    CFG = CFGS["cg"]
+    plain = _maker(mesh, span, "cg", "reference", model_params)
 
     def scheduled(n_bars):
         quench_end = np.round(np.linspace(20.0, 100.0, n_bars)).astype(int)
@@ -299,258 +338,105 @@ def scheduled_bench(args):
                                      "probes at the two surfaces and the mid-plane, every 10 steps"},
            "parent": "the parent commit's own checkout and tool, child process of the same session"
                      if parent else None,
-           "kernel": KERNEL_RECORD, "sizes": rows}
+           "kernel": kernel_record("cg", "reference"), "sizes": rows}
     out = args.out or os.path.join(ROOT, "profiles", "ensemble_schedule_bench.json")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as fh:
-        json.dump(res, fh, indent=1)
-        fh.write("\n")
+    _write(out, res)
     print(json.dumps({"out": out}))
 
 
-def dg_bench(args):
+def bench(args, mode):
+    """The mode's ensemble per size, the ensemble it is held against, the sequential path; one JSON."""
     from geometry import graded_bar
     from main import model_params
-    from tvfem import ThermoViscoEnsemble
 
     mesh = graded_bar()
     n_nodes = mesh.num_vertices
     n_cells = n_nodes - 1
     span = (0.0, args.steps * 0.1)
+    fam, model = mode["cell"]
+    paper = model != "reference"
+    families = FAMILIES[fam]
+    params = dict(model_params) if mode["T_0"] is None else dict(model_params, T_0=mode["T_0"])
+    make = _maker(mesh, span, fam, model, params)
+    workload = {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "steps": args.steps, "dt": 0.1,
+                "htc": "linspace(50, 1000, n_bars)", "families": families, "reps": args.reps}
+    if mode["baseline"]:
+        workload["n_cells"] = n_cells
+    if paper:
+        workload.update(T_0=params["T_0"], model_mode="paper")
+    elif fam == "dg":
+        workload["n_dofs_T"] = 2 * n_cells
+    if model == "exact":  # a last look at the state the timed kernel leaves: finite in exact mode at this T_0
+        probe = make(64)
+        probe.solve(args.steps)
+        sigma = probe.get_field("sigma")
+        probe.close()
+        if not np.all(np.isfinite(sigma)):
+            sys.exit("exact relaxation: sigma is not finite")
+        workload.update(relaxation="exact", sigma_abs_max_exact_64_bars=float(np.abs(sigma).max()),
+                        taylor_ensemble="the same ensemble with relaxation=taylor, same process; at this T_0 its "
+                                        "stress overflows (the thermal problem and the Newton counts are the "
+                                        "same), so only its time is used")
 
-    def make(cfg):
-        def ensemble(n_bars):
-            ens = ThermoViscoEnsemble(mesh, span, 0.1, cfg, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)))
-            ens.setup()
-            return ens
-        return ensemble
-
-    dg = _time_ensembles(make(CFG_DG), args.sizes, args.steps, args.reps)
-    cg = _time_ensembles(make(CFG), args.sizes, args.steps, args.reps)
+    timed = _time_ensembles(make, args.sizes, args.steps, args.reps)
+    base = None
+    if mode["baseline"]:
+        base = _time_ensembles(_maker(mesh, span, *mode["baseline"], params), args.sizes, args.steps, args.reps)
     rows = []
-    for d, c in zip(dg, cg):
-        bar_steps = d["n_bars"] * args.steps
-        nbytes = bar_steps * (n_cells * DG_BYTES_CELL_NEWTON * d["newton_its_per_step"]
-                              + 2 * n_cells * DG_BYTES_TDOF_STEP + n_nodes * DG_BYTES_NODE_STEP)
-        cg_bytes = bar_steps * n_nodes * (BYTES_NODE_NEWTON * c["newton_its_per_step"] + BYTES_NODE_STEP)
-        row = dict(d, bar_steps_per_s=bar_steps / d["wall_s"], algorithmic_bytes=nbytes,
-                   hbm_fraction_of_8TBps=nbytes / d["wall_s"] / HBM_PEAK,
-                   us_per_T_dof_and_step_of_a_lane=d["wall_s"] / args.steps / (2 * n_cells) * 1e6,
-                   cg_ensemble=dict(c, bar_steps_per_s=bar_steps / c["wall_s"], algorithmic_bytes=cg_bytes),
-                   dg_over_cg_time=d["wall_s"] / c["wall_s"], dg_over_cg_algorithmic_bytes=nbytes / cg_bytes)
-        rows.append(row)
-        print(f"DG ensemble {d['n_bars']:6d} bars: {d['wall_s'] * 1e3:9.2f} ms  {row['bar_steps_per_s']:12.4g} "
-              f"bar-steps/s  {d['newton_its_per_step']:.2f} its/step  {row['hbm_fraction_of_8TBps']:.2%} of HBM peak;  "
-              f"CG {c['wall_s'] * 1e3:9.2f} ms  time ratio {row['dg_over_cg_time']:.3f}  "
-              f"byte ratio {row['dg_over_cg_algorithmic_bytes']:.3f}", flush=True)
-
-    seq_wall, _ = _time_sequential(mesh, span, CFG_DG, args.seq_bars, args.steps)  # the same bar, DG / CG
-    seq_rate = args.seq_bars * args.steps / seq_wall
-    print(f"sequential {args.seq_bars} DG/CG bars: {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
-    for r in rows:
-        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
-    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "n_cells": n_cells,
-                        "n_dofs_T": 2 * n_cells, "steps": args.steps, "dt": 0.1, "htc": "linspace(50, 1000, n_bars)",
-                        "families": "DG1/CG1", "reps": args.reps},
-           "bytes_model": {"per_cell_newton_iteration": DG_BYTES_CELL_NEWTON, "per_T_dof_step": DG_BYTES_TDOF_STEP,
-                           "per_node_step": DG_BYTES_NODE_STEP},
-           "kernel": DG_KERNEL_RECORD, "ensemble": rows,
-           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
-                          "timed": "ThermoViscoProblem DG1/CG1: solve() and a final field read per bar; context "
-                                   "creation and setup left out"},
-           "floor_ratio_at_4096": FLOOR}
-    at = [r for r in rows if r["n_bars"] == 4096]
-    if at:
-        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
-        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
-    out = args.out or os.path.join(ROOT, "profiles", "ensemble_dg_bench.json")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out, "w") as fh:
-        json.dump(res, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps({"out": out, "ratio_at_4096": res.get("ratio_at_4096")}))
-    if at and res["ratio_at_4096"] < FLOOR:
-        sys.exit(f"DG ensemble below the {FLOOR:g}x floor at 4096 bars")
-
-
-def paper_bench(args):
-    from geometry import graded_bar
-    from main import model_params
-    from tvfem import ThermoViscoEnsemble
-
-    mesh = graded_bar()
-    n_nodes = mesh.num_vertices
-    n_cells = n_nodes - 1
-    span = (0.0, args.steps * 0.1)
-    cfg = CFG_DG if args.dg else CFG
-    families = "DG1/CG1" if args.dg else "CG1/CG1"
-
-    def make(mode):
-        def ensemble(n_bars):
-            ens = ThermoViscoEnsemble(mesh, span, 0.1, cfg, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)),
-                                      model_mode=mode)
-            ens.setup()
-            return ens
-        return ensemble
-
-    def model_bytes(its, paper):
-        if args.dg:
-            return (n_cells * DG_BYTES_CELL_NEWTON * its
-                    + 2 * n_cells * (PAPER_DG_BYTES_TDOF_STEP if paper else DG_BYTES_TDOF_STEP)
-                    + n_nodes * (PAPER_DG_BYTES_NODE_STEP if paper else DG_BYTES_NODE_STEP))
-        return n_nodes * (BYTES_NODE_NEWTON * its + (PAPER_BYTES_NODE_STEP if paper else BYTES_NODE_STEP))
-
-    pap = _time_ensembles(make("paper"), args.sizes, args.steps, args.reps)
-    ref = _time_ensembles(make("reference"), args.sizes, args.steps, args.reps)
-    rows = []
-    for p, r in zip(pap, ref):
-        bar_steps = p["n_bars"] * args.steps
-        nbytes = bar_steps * model_bytes(p["newton_its_per_step"], True)
-        ref_bytes = bar_steps * model_bytes(r["newton_its_per_step"], False)
-        row = dict(p, bar_steps_per_s=bar_steps / p["wall_s"], algorithmic_bytes=nbytes,
-                   hbm_fraction_of_8TBps=nbytes / p["wall_s"] / HBM_PEAK,
-                   reference_ensemble=dict(r, bar_steps_per_s=bar_steps / r["wall_s"], algorithmic_bytes=ref_bytes),
-                   paper_over_reference_time=p["wall_s"] / r["wall_s"],
-                   paper_over_reference_algorithmic_bytes=nbytes / ref_bytes)
-        rows.append(row)
-        print(f"paper {families} ensemble {p['n_bars']:6d} bars: {p['wall_s'] * 1e3:9.2f} ms  "
-              f"{row['bar_steps_per_s']:12.4g} bar-steps/s  {p['newton_its_per_step']:.2f} its/step  "
-              f"{row['hbm_fraction_of_8TBps']:.2%} of HBM peak;  reference {r['wall_s'] * 1e3:9.2f} ms  "
-              f"time ratio {row['paper_over_reference_time']:.3f}  "
-              f"byte ratio {row['paper_over_reference_algorithmic_bytes']:.3f}", flush=True)
-
-    seq_wall, _ = _time_sequential(mesh, span, cfg, args.seq_bars, args.steps, model_mode="paper")
-    seq_rate = args.seq_bars * args.steps / seq_wall
-    print(f"sequential {args.seq_bars} paper-mode {families} bar(s): {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s",
-          flush=True)
-    for r in rows:
-        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
-    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "n_cells": n_cells, "steps": args.steps,
-                        "dt": 0.1, "htc": "linspace(50, 1000, n_bars)", "T_0": model_params["T_0"],
-                        "families": families, "model_mode": "paper", "reps": args.reps},
-           "bytes_model": ({"per_cell_newton_iteration": DG_BYTES_CELL_NEWTON,
-                            "per_T_dof_step": PAPER_DG_BYTES_TDOF_STEP, "per_node_step": PAPER_DG_BYTES_NODE_STEP,
-                            "reference_per_T_dof_step": DG_BYTES_TDOF_STEP,
-                            "reference_per_node_step": DG_BYTES_NODE_STEP} if args.dg else
-                           {"per_node_newton_iteration": BYTES_NODE_NEWTON, "per_node_step": PAPER_BYTES_NODE_STEP,
-                            "reference_per_node_step": BYTES_NODE_STEP}),
-           "kernel": PAPER_DG_KERNEL_RECORD if args.dg else PAPER_KERNEL_RECORD, "ensemble": rows,
-           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
-                          "timed": f"ThermoViscoProblem {families} model_mode=paper: solve() and a final field read "
-                                   "per bar; context creation and setup left out"},
-           "floor_ratio_at_4096": FLOOR}
-    at = [r for r in rows if r["n_bars"] == 4096]
-    if at:
-        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
-        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
-    # one file for both pairings, keyed by the families: a run replaces its own key and keeps the other
-    out = args.out or os.path.join(ROOT, "profiles", "ensemble_paper_bench.json")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    both = {}
-    if os.path.exists(out):
-        with open(out) as fh:
-            both = json.load(fh)
-    both[families] = res
-    with open(out, "w") as fh:
-        json.dump(both, fh, indent=1, sort_keys=True)
-        fh.write("\n")
-    print(json.dumps({"out": out, "ratio_at_4096": res.get("ratio_at_4096")}))
-    if at and res["ratio_at_4096"] < FLOOR:
-        sys.exit(f"paper ensemble below the {FLOOR:g}x floor at 4096 bars")
-
-
-def exact_bench(args):
-    from geometry import graded_bar
-    from main import model_params
-    from tvfem import ThermoViscoEnsemble
-
-    mesh = graded_bar()
-    n_nodes = mesh.num_vertices
-    n_cells = n_nodes - 1
-    span = (0.0, args.steps * 0.1)
-    cfg = CFG_DG if args.dg else CFG
-    families = "DG1/CG1" if args.dg else "CG1/CG1"
-    hot = dict(model_params, T_0=EXACT_T_0)
-
-    def make(relaxation):
-        def ensemble(n_bars):
-            ens = ThermoViscoEnsemble(mesh, span, 0.1, cfg, dict(hot, htc=np.linspace(50.0, 1000.0, n_bars)),
-                                      model_mode="paper", relaxation=relaxation)
-            ens.setup()
-            return ens
-        return ensemble
-
-    # a last look at the state the timed kernel leaves: finite in exact mode at this T_0
-    probe = make("exact")(64)
-    probe.solve(args.steps)
-    sigma = probe.get_field("sigma")
-    probe.close()
-    if not np.all(np.isfinite(sigma)):
-        sys.exit("exact relaxation: sigma is not finite")
-    ex = _time_ensembles(make("exact"), args.sizes, args.steps, args.reps)
-    ta = _time_ensembles(make("taylor"), args.sizes, args.steps, args.reps)
-    rows = []
-    for e, t in zip(ex, ta):
-        bar_steps = e["n_bars"] * args.steps
-        its = e["newton_its_per_step"]
-        if args.dg:  # the bytes of paper mode: the relaxation moves none
-            per_bar_step = (n_cells * DG_BYTES_CELL_NEWTON * its + 2 * n_cells * PAPER_DG_BYTES_TDOF_STEP
-                            + n_nodes * PAPER_DG_BYTES_NODE_STEP)
+    for i, r in enumerate(timed):
+        bar_steps = r["n_bars"] * args.steps
+        nbytes = bar_steps * bytes_per_bar_step(fam, paper, r["newton_its_per_step"], n_nodes)
+        row = dict(r, bar_steps_per_s=bar_steps / r["wall_s"], algorithmic_bytes=nbytes,
+                   hbm_fraction_of_8TBps=nbytes / r["wall_s"] / HBM_PEAK)
+        line = (f"{mode['label']} ensemble {r['n_bars']:6d} bars: {r['wall_s'] * 1e3:9.2f} ms  "
+                f"{row['bar_steps_per_s']:12.4g} bar-steps/s  {r['newton_its_per_step']:.2f} Newton its/step  "
+                f"{row['hbm_fraction_of_8TBps']:.2%} of HBM peak")
+        if base is None:
+            del row["spread"]  # ensemble_bench.json holds the three wall times
         else:
-            per_bar_step = n_nodes * (BYTES_NODE_NEWTON * its + PAPER_BYTES_NODE_STEP)
-        nbytes = bar_steps * per_bar_step
-        row = dict(e, bar_steps_per_s=bar_steps / e["wall_s"], algorithmic_bytes=nbytes,
-                   hbm_fraction_of_8TBps=nbytes / e["wall_s"] / HBM_PEAK,
-                   taylor_ensemble=dict(t, bar_steps_per_s=bar_steps / t["wall_s"]),
-                   exact_over_taylor_time=e["wall_s"] / t["wall_s"])
+            b = base[i]
+            row[mode["baseline_key"]] = dict(b, bar_steps_per_s=bar_steps / b["wall_s"])
+            row[mode["time_ratio"]] = r["wall_s"] / b["wall_s"]
+            line += f";  {mode['baseline_label']} {b['wall_s'] * 1e3:9.2f} ms  time ratio {row[mode['time_ratio']]:.3f}"
+            if mode["bytes_ratio"]:
+                bfam, bmodel = mode["baseline"]
+                bbytes = bar_steps * bytes_per_bar_step(bfam, bmodel != "reference", b["newton_its_per_step"], n_nodes)
+                row[mode["baseline_key"]]["algorithmic_bytes"] = bbytes
+                row[mode["bytes_ratio"]] = nbytes / bbytes
+                line += f"  byte ratio {row[mode['bytes_ratio']]:.3f}"
+            if not paper:
+                row["us_per_T_dof_and_step_of_a_lane"] = r["wall_s"] / args.steps / (2 * n_cells) * 1e6
         rows.append(row)
-        print(f"exact {families} ensemble {e['n_bars']:6d} bars: {e['wall_s'] * 1e3:9.2f} ms  "
-              f"{row['bar_steps_per_s']:12.4g} bar-steps/s  {its:.2f} its/step  "
-              f"{row['hbm_fraction_of_8TBps']:.2%} of HBM peak;  taylor {t['wall_s'] * 1e3:9.2f} ms  "
-              f"time ratio {row['exact_over_taylor_time']:.3f}", flush=True)
+        print(line.lstrip(), flush=True)
 
-    # the single-problem path has no exact mode: one Taylor paper-mode bar, at main.py's T_0 = 800 K so that it
-    # stays finite over all the steps
-    seq_wall, _ = _time_sequential(mesh, span, cfg, args.seq_bars, args.steps, model_mode="paper")
-    seq_rate = args.seq_bars * args.steps / seq_wall
-    print(f"sequential {args.seq_bars} paper-mode {families} bar(s) at T_0 = {model_params['T_0']:g} K: "
-          f"{seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
+    # the same work one bar after another (what a parameter study costs without the ensemble).  The
+    # single-problem path has no exact mode: a Taylor paper-mode bar, at main.py's T_0 so that it stays finite
+    seq_wall, seq_total = _time_sequential(mesh, span, CFGS[fam], args.seq_bars, args.steps,
+                                           **(dict(model_mode="paper") if paper else {}))
+    seq_rate = args.seq_bars * args.steps / seq_wall  # the time loops alone: context creation left out
+    print(f"sequential {args.seq_bars} {mode['label']} bar(s): ".replace("  ", " ")
+          + f"{seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
     for r in rows:
         r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
-    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "n_cells": n_cells, "steps": args.steps,
-                        "dt": 0.1, "htc": "linspace(50, 1000, n_bars)", "T_0": EXACT_T_0, "families": families,
-                        "model_mode": "paper", "relaxation": "exact", "reps": args.reps,
-                        "taylor_ensemble": "the same ensemble with relaxation=taylor, same process; at this T_0 its "
-                                           "stress overflows (the thermal problem and the Newton counts are the "
-                                           "same), so only its time is used",
-                        "sigma_abs_max_exact_64_bars": float(np.abs(sigma).max())},
-           "bytes_model": "paper mode's (tools/ensemble_bench.py --paper): the relaxation moves no byte",
-           "kernel": EXACT_DG_KERNEL_RECORD if args.dg else EXACT_KERNEL_RECORD, "ensemble": rows,
-           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
-                          "T_0": model_params["T_0"],
-                          "timed": f"ThermoViscoProblem {families} model_mode=paper (Taylor; no exact mode exists "
-                                   f"there) at T_0 = {model_params['T_0']:g} K, inside the Taylor limit, all "
-                                   f"{args.steps} steps: solve() and a final field read per bar; context creation "
-                                   "and setup left out"},
-           "floor_ratio_at_4096": FLOOR}
+    sequential = {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
+                  "timed": mode["timed"].format(families=families, T_0=model_params["T_0"], steps=args.steps)}
+    if base is None:
+        sequential["wall_s_with_context_creation"] = seq_total
+    if model == "exact":
+        sequential["T_0"] = model_params["T_0"]
+    res = {"workload": workload, "bytes_model": mode["bytes_model"]}
+    if base is not None:
+        res["kernel"] = kernel_record(fam, model)
+    res.update(ensemble=rows, sequential=sequential, floor_ratio_at_4096=FLOOR)
     at = [r for r in rows if r["n_bars"] == 4096]
     if at:
         res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
         print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
-    # one file for both pairings, keyed by the families: a run replaces its own key and keeps the other
-    out = args.out or os.path.join(ROOT, "profiles", "ensemble_exact_bench.json")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    both = {}
-    if os.path.exists(out):
-        with open(out) as fh:
-            both = json.load(fh)
-    both[families] = res
-    with open(out, "w") as fh:
-        json.dump(both, fh, indent=1, sort_keys=True)
-        fh.write("\n")
+    out = args.out or os.path.join(ROOT, "profiles", mode["out"])
+    _write(out, res, families if mode["keyed"] else None)
     print(json.dumps({"out": out, "ratio_at_4096": res.get("ratio_at_4096")}))
     if at and res["ratio_at_4096"] < FLOOR:
-        sys.exit(f"exact ensemble below the {FLOOR:g}x floor at 4096 bars")
+        sys.exit(f"{mode['label']} ensemble below the {FLOOR:g}x floor at 4096 bars".lstrip())
 
 
 def main():
@@ -575,67 +461,12 @@ def main():
                     help="the exact-relaxation paper ensemble (with --dg: DG1 / CG1) at T_0 = 873 K against the "
                          "paper-mode ensemble and one sequential paper-mode bar")
     args = ap.parse_args()
-    if args.seq_bars is None:
-        args.seq_bars = 1 if args.paper or args.exact else 4
-    if args.exact:
-        return exact_bench(args)
-    if args.paper:
-        return paper_bench(args)
-    if args.scheduled:
+    if args.scheduled and not (args.paper or args.exact):
         return scheduled_bench(args)
-    if args.dg:
-        return dg_bench(args)
-    args.out = args.out or os.path.join(ROOT, "profiles", "ensemble_bench.json")
-
-    from geometry import graded_bar
-    from main import model_params
-    from tvfem import ThermoViscoEnsemble
-
-    mesh = graded_bar()
-    n_nodes = mesh.num_vertices
-    span = (0.0, args.steps * 0.1)
-
-    def ensemble(n_bars):
-        ens = ThermoViscoEnsemble(mesh, span, 0.1, CFG, dict(model_params, htc=np.linspace(50.0, 1000.0, n_bars)))
-        ens.setup()
-        return ens
-
-    rows = []
-    for r in _time_ensembles(ensemble, args.sizes, args.steps, args.reps):
-        n_bars, wall, its = r["n_bars"], r["wall_s"], r["newton_its_per_step"]
-        bar_steps = n_bars * args.steps
-        nbytes = bar_steps * n_nodes * (BYTES_NODE_NEWTON * its + BYTES_NODE_STEP)
-        rows.append({"n_bars": n_bars, "wall_s": wall, "wall_s_min": r["wall_s_min"], "wall_s_max": r["wall_s_max"],
-                     "bar_steps_per_s": bar_steps / wall, "newton_its_per_step": its,
-                     "algorithmic_bytes": nbytes, "hbm_fraction_of_8TBps": nbytes / wall / HBM_PEAK})
-        print(f"ensemble {n_bars:6d} bars: {wall * 1e3:9.2f} ms  {bar_steps / wall:12.4g} bar-steps/s  "
-              f"{its:.2f} Newton its/step  {nbytes / wall / HBM_PEAK:.2%} of HBM peak", flush=True)
-
-    # the same work one bar after another (what a parameter study costs without the ensemble)
-    seq_wall, seq_total = _time_sequential(mesh, span, CFG, args.seq_bars, args.steps)
-    seq_rate = args.seq_bars * args.steps / seq_wall  # the time loops alone: context creation left out
-    print(f"sequential {args.seq_bars} bars: {seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
-    for r in rows:
-        r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
-    res = {"workload": {"mesh": "geometry.graded_bar", "n_nodes": n_nodes, "steps": args.steps, "dt": 0.1,
-                        "htc": "linspace(50, 1000, n_bars)", "families": "CG1/CG1", "reps": args.reps},
-           "bytes_model": {"per_node_newton_iteration": BYTES_NODE_NEWTON, "per_node_step": BYTES_NODE_STEP},
-           "ensemble": rows,
-           "sequential": {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
-                          "wall_s_with_context_creation": seq_total,
-                          "timed": "solve() and a final field read per bar; context creation and setup left out"},
-           "floor_ratio_at_4096": FLOOR}
-    at = [r for r in rows if r["n_bars"] == 4096]
-    if at:
-        res["ratio_at_4096"] = at[0]["ratio_to_sequential"]
-        print(f"ratio at 4096 bars: {res['ratio_at_4096']:.1f}x (floor {FLOOR:g}x)")
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as fh:
-        json.dump(res, fh, indent=1)
-        fh.write("\n")
-    print(json.dumps({"out": args.out, "ratio_at_4096": res.get("ratio_at_4096")}))
-    if at and res["ratio_at_4096"] < FLOOR:
-        sys.exit(f"ensemble below the {FLOOR:g}x floor at 4096 bars")
+    mode = mode_of(args)
+    if args.seq_bars is None:
+        args.seq_bars = mode["seq_bars"]
+    bench(args, mode)
 
 
 if __name__ == "__main__":
