@@ -1273,6 +1273,21 @@ int tv_set_dirichlet(void* ctx, int enable, double value) {
 }
 
 
+// read by visco_setup at every update (ViscoConst is rebuilt there and no graph
+// holds it), so the next update is the first that sees the new value
+int tv_set_relaxation(void* ctx, int relaxation) {
+  Ctx* c = static_cast<Ctx*>(ctx);
+  if (!c) return TV_ERR_ARG;
+  if (relaxation != TV_RELAX_TAYLOR && relaxation != TV_RELAX_EXACT)
+    return c->fail(TV_ERR_ARG, "relaxation: TV_RELAX_TAYLOR (0) or TV_RELAX_EXACT (1)");
+  if (relaxation == TV_RELAX_EXACT && c->O.model_mode != TV_MODEL_PAPER)
+    return c->fail(TV_ERR_STATE, "relaxation: the exact relaxation needs paper mode (model_mode = TV_MODEL_PAPER; "
+                                 "reference mode is the reference's code, its Taylor exponential included)");
+  c->relaxation = relaxation;
+  return TV_OK;
+}
+
+
 int tv_sync(void* ctx) {
   Ctx* c = static_cast<Ctx*>(ctx);
   if (!c) return TV_ERR_ARG;

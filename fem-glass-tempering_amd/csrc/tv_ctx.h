@@ -151,6 +151,7 @@ struct Ctx {
   double dir_value = 0.0;
   double *dB = nullptr, *dtmp = nullptr;
   double* Tfo = nullptr;  // paper mode, mixed families: previous Tf per T dof
+  int relaxation = TV_RELAX_TAYLOR;  // tv_set_relaxation: TV_RELAX_EXACT makes visco_setup's model id 2
   Output* out = nullptr;  // time-series output (tv_output_*)
   // geometric multigrid (options.preconditioner = TV_PC_GMG): levels 1.. (level 0 = cg)
   bool mg_on = false;

@@ -177,7 +177,7 @@ struct ViscoConst {
   double lambda_m[6], m_n[6], lambda_g[6], g_n[6], lambda_k[6], k_n[6];
   double chi;   // ViscoelasticModel.py:15 (Eq. 25, paper mode only)
   int paper;    // model_mode: 0 reference semantics (quirks Q1-Q4 kept), 1 paper, 2 paper with the exact
-                // exponential relaxation (ensemble kernels only: tv_create refuses it)
+                // exponential relaxation (ensembles: TV_MODEL_PAPER_EXACT; a single problem: tv_set_relaxation)
 };
 // every ViscoConst is filled here: `model` becomes `paper`, inv_dim is 1.0 / dim (an ensemble bar: dim 1)
 void fill_visco_const(ViscoConst& k, const tv_params& P, int dim, int model);

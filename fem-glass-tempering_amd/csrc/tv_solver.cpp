@@ -604,7 +604,9 @@ void fill_visco_const(ViscoConst& k, const tv_params& P, int dim, int model) {
 }
 
 void visco_setup(Ctx* c, ViscoConst& k, ViscoFields& v) {
-  fill_visco_const(k, c->P, c->dim, (c->O.model_mode == TV_MODEL_PAPER) ? 1 : 0);
+  // model id (ViscoConst::paper): tv_set_relaxation admits TV_RELAX_EXACT on paper contexts only
+  const int model = (c->O.model_mode == TV_MODEL_PAPER) ? (c->relaxation == TV_RELAX_EXACT ? 2 : 1) : 0;
+  fill_visco_const(k, c->P, c->dim, model);
   std::memset(&v, 0, sizeof(v));
   v.sT = field_stride(c, 0);
   v.sS = field_stride(c, 1);

@@ -35,13 +35,13 @@
 namespace tv {
 namespace {
 
-template <int D, bool ALL, bool LEAN, bool PAPER = false>
+template <int D, bool ALL, bool LEAN, bool PAPER = false, bool EXACT = false>
 __device__ __forceinline__ void fused_loop(const ViscoConst& c, const ViscoFields& f) {
   bool dirty = false;
   for (int64_t t = blockIdx.x * (int64_t)kBlock + threadIdx.x; t < f.n; t += (int64_t)gridDim.x * kBlock) {
     const int64_t dT = f.off_T + t;
     const TState ts = t_part<ALL, PAPER>(c, f, dT);
-    s_part<D, ALL, LEAN, PAPER>(c, f, f.off_S + t, ts, dirty);
+    s_part<D, ALL, LEAN, PAPER, EXACT>(c, f, f.off_S + t, ts, dirty);
     if (f.copy_Tprev) f.Tp[dT] = ts.T;  // TVP:378-379, T_prev is not read after this point
   }
   if (dirty) *f.tflag = 1;
@@ -57,6 +57,15 @@ __global__ __launch_bounds__(kBlock) void k_visco_fused(ViscoConst c, ViscoField
   // read once: a flag raised later in this launch changes nothing (see s_part)
   if (*f.tflag == 0) fused_loop<D, ALL, true>(c, f);
   else fused_loop<D, ALL, false>(c, f);
+}
+
+// paper mode with the exact relaxation (ViscoConst::paper == 2, tv_set_relaxation):
+// a kernel of its own, chosen on the host, so the kernel above is the same code
+// with or without it.  t_part does not see the relaxation.
+template <int D, bool ALL>
+__global__ __launch_bounds__(kBlock) void k_visco_fused_exact(ViscoConst c, ViscoFields f) {
+  if (!newton_gate_open(f.gate)) return;
+  fused_loop<D, ALL, false, true, true>(c, f);
 }
 
 // mixed families, T pass; in paper mode it also keeps the previous step's Tf
@@ -76,7 +85,7 @@ __global__ __launch_bounds__(kBlock) void k_visco_T(ViscoConst c, ViscoFields f)
 
 // mixed families: sigma dof s reads the T-family values of the dof that the
 // last cell written by fem::interpolate assigns to it (f.map).
-template <int D, bool ALL, bool LEAN, bool PAPER = false>
+template <int D, bool ALL, bool LEAN, bool PAPER = false, bool EXACT = false>
 __device__ __forceinline__ void s_loop(const ViscoConst& c, const ViscoFields& f) {
   bool dirty = false;
   for (int64_t s = blockIdx.x * (int64_t)kBlock + threadIdx.x; s < f.n; s += (int64_t)gridDim.x * kBlock) {
@@ -87,7 +96,7 @@ __device__ __forceinline__ void s_loop(const ViscoConst& c, const ViscoFields& f
     ts.Tf = f.Tf[t];
     ts.Tfo = PAPER ? f.Tfo[t] : ts.Tf;
     ts.xi = f.xi[t];
-    s_part<D, ALL, LEAN, PAPER>(c, f, f.off_S + s, ts, dirty);
+    s_part<D, ALL, LEAN, PAPER, EXACT>(c, f, f.off_S + s, ts, dirty);
   }
   if (dirty) *f.tflag = 1;
 }
@@ -98,6 +107,13 @@ __global__ __launch_bounds__(kBlock) void k_visco_S(ViscoConst c, ViscoFields f)
   if (c.paper) s_loop<D, ALL, false, true>(c, f);
   else if (*f.tflag == 0) s_loop<D, ALL, true>(c, f);
   else s_loop<D, ALL, false>(c, f);
+}
+
+// the sigma pass with the exact relaxation (see k_visco_fused_exact)
+template <int D, bool ALL>
+__global__ __launch_bounds__(kBlock) void k_visco_S_exact(ViscoConst c, ViscoFields f) {
+  if (!newton_gate_open(f.gate)) return;
+  s_loop<D, ALL, false, true, true>(c, f);
 }
 
 __global__ __launch_bounds__(kBlock) void k_copy_gated(double* __restrict__ d, const double* __restrict__ s, int64_t n,
@@ -116,7 +132,11 @@ int blocks_for(int64_t n) {
 
 void launch_visco(int dim, int all, const ViscoConst& c, const ViscoFields& f, hipStream_t s) {
   const int b = blocks_for(f.n);
-#define TV_V(D, A) hipLaunchKernelGGL((k_visco_fused<D, A>), dim3(b), dim3(kBlock), 0, s, c, f)
+#define TV_V(D, A)                                                                                   \
+  do {                                                                                               \
+    if (c.paper == 2) hipLaunchKernelGGL((k_visco_fused_exact<D, A>), dim3(b), dim3(kBlock), 0, s, c, f); \
+    else hipLaunchKernelGGL((k_visco_fused<D, A>), dim3(b), dim3(kBlock), 0, s, c, f);               \
+  } while (0)
   if (dim == 1) { if (all) TV_V(1, true); else TV_V(1, false); }
   else if (dim == 2) { if (all) TV_V(2, true); else TV_V(2, false); }
   else { if (all) TV_V(3, true); else TV_V(3, false); }
@@ -137,7 +157,11 @@ void launch_visco_Tpass(int dim, int all, const ViscoConst& c, const ViscoFields
 
 void launch_visco_Spass(int dim, int all, const ViscoConst& c, const ViscoFields& f, hipStream_t s) {
   const int b = blocks_for(f.n);
-#define TV_V(D, A) hipLaunchKernelGGL((k_visco_S<D, A>), dim3(b), dim3(kBlock), 0, s, c, f)
+#define TV_V(D, A)                                                                               \
+  do {                                                                                           \
+    if (c.paper == 2) hipLaunchKernelGGL((k_visco_S_exact<D, A>), dim3(b), dim3(kBlock), 0, s, c, f); \
+    else hipLaunchKernelGGL((k_visco_S<D, A>), dim3(b), dim3(kBlock), 0, s, c, f);               \
+  } while (0)
   if (dim == 1) { if (all) TV_V(1, true); else TV_V(1, false); }
   else if (dim == 2) { if (all) TV_V(2, true); else TV_V(2, false); }
   else { if (all) TV_V(3, true); else TV_V(3, false); }

@@ -16,6 +16,7 @@ TV_OK, TV_ERR_ARG, TV_ERR_HIP, TV_ERR_NOT_CONVERGED, TV_ERR_KSP, TV_ERR_STATE, T
 TV_CG, TV_DG = 0, 1
 TV_PCG_AUTO, TV_PCG_KSPCG, TV_PCG_SINGLE_REDUCTION = 0, 1, 2
 TV_MODEL_REFERENCE, TV_MODEL_PAPER, TV_MODEL_PAPER_EXACT = 0, 1, 2  # PAPER_EXACT: ensembles only
+TV_RELAX_TAYLOR, TV_RELAX_EXACT = 0, 1  # tv_set_relaxation (single-problem contexts)
 TV_PC_JACOBI, TV_PC_GMG, TV_PC_AMG = 0, 1, 2
 TV_DG_KERNEL_AUTO, TV_DG_KERNEL_TILE, TV_DG_KERNEL_CELLS = 0, 1, 2
 TV_MG_COUPLING_AUTO, TV_MG_COUPLING_GLOBAL, TV_MG_COUPLING_LOCAL = 0, 1, 2
@@ -38,7 +39,7 @@ EXPORTS = [
     "tv_jacobian_diag", "tv_precond_apply", "tv_solve_T", "tv_visco_update", "tv_step", "tv_comm_unique_id_size",
     "tv_comm_get_unique_id", "tv_comm_init", "tv_comm_init_stub", "tv_comm_init_loopback", "tv_comm_check", "tv_comm_time", "tv_halo_exchange", "tv_time_kernel", "tv_kernel_bytes", "tv_kernel_timing", "tv_kernel_stats",
     "tv_last_stats", "tv_last_converged", "tv_comm_init_host", "tv_partition_layout", "tv_pcg_variant",
-    "tv_set_dirichlet", "tv_get_options", "tv_set_newton_tolerances", "tv_set_ksp_tolerances",
+    "tv_set_dirichlet", "tv_set_relaxation", "tv_get_options", "tv_set_newton_tolerances", "tv_set_ksp_tolerances",
     "tv_output_open", "tv_output_open_named", "tv_output_write", "tv_output_close", "tv_xdmf_open",
     "tv_xdmf_add_field", "tv_xdmf_append", "tv_xdmf_close",
     "tv_ensemble_create", "tv_ensemble_destroy", "tv_ensemble_set_initial_condition", "tv_ensemble_step",
@@ -180,6 +181,7 @@ def load_library():
         "tv_partition_layout": (C.c_int, [C.POINTER(MeshDesc), i64p]),
         "tv_pcg_variant": (C.c_int, [vp, ip]),
         "tv_set_dirichlet": (C.c_int, [vp, C.c_int, C.c_double]),
+        "tv_set_relaxation": (C.c_int, [vp, C.c_int]),
         "tv_get_options": (C.c_int, [vp, C.POINTER(Options)]),
         "tv_set_newton_tolerances": (C.c_int, [vp, C.c_double, C.c_double, C.c_int, C.c_int]),
         "tv_set_ksp_tolerances": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_int]),

@@ -73,7 +73,8 @@ T, Tf, phi, xi, the Newton counts, the failure contract, schedules, histories
 and the state fields are those of a paper ensemble; only ``sigma`` and the four
 partial-stress fields differ.  ``relaxation="exact"`` with
 ``model_mode="reference"`` raises ``ValueError``; ``ens.relaxation`` holds the
-choice.  The single-problem path (``ThermoViscoProblem``) has no exact mode.
+choice.  The single-problem path has the same switch:
+``ThermoViscoProblem(..., model_mode="paper", relaxation="exact")``.
 """
 from __future__ import annotations
 

@@ -112,7 +112,8 @@ class ThermoViscoProblem:
                  write_output: bool | None = None, output_dir: str = "output", preconditioner: str = "jacobi",
                  mg_levels: int = 0, dg_kernel: str = "auto", dg_tile_chunk: int = 0,
                  mg_replicate_nodes: int = 0, ksp_fixed_its: int = 0, newton_fixed_its: int = 0,
-                 cell_parts=None, mg_coupling: str = "auto", ksp_max_it: int = 10000) -> None:
+                 cell_parts=None, mg_coupling: str = "auto", ksp_max_it: int = 10000,
+                 relaxation: str = "taylor") -> None:
         if isinstance(mesh_path, (RectilinearMesh, UnstructuredMesh)):
             self.mesh = mesh_path
         elif isinstance(mesh_path, str):
@@ -136,7 +137,9 @@ class ThermoViscoProblem:
         if model_mode not in ("reference", "paper"):
             raise ValueError("model_mode must be 'reference' (the reference as it runs) or 'paper'")
         self.model_mode = model_mode
-        self.write_output = self.WRITE_OUTPUT_DEFAULT if write_output is None else bool(write_output)
+        self._check_relaxation(relaxation)
+        self.relaxation = relaxation
+        self.write_output =self.WRITE_OUTPUT_DEFAULT if write_output is None else bool(write_output)
         self.output_dir = output_dir
         self._output_open = False
         if preconditioner not in ("jacobi", "gmg", "amg"):
@@ -263,6 +266,11 @@ class ThermoViscoProblem:
             create = lib.tv_create_unstructured if um else lib.tv_create
             N.check(create(C.byref(desc), C.byref(fe), C.byref(params), C.byref(opts), device, C.byref(ctx)))
         self._ctx = ctx
+        try:
+            self._apply_relaxation(self.relaxation)
+        except Exception:
+            self.close()
+            raise
         self.materialize = materialize
         self._bs = {}
         for name, fid in N.FIELD_ID.items():
@@ -306,6 +314,25 @@ class ThermoViscoProblem:
         v = C.c_int()
         N.check(self._lib.tv_pcg_variant(self._ctx, C.byref(v)), self._ctx)
         return "single" if v.value == N.TV_PCG_SINGLE_REDUCTION else "kspcg"
+
+    def _check_relaxation(self, relaxation) -> None:
+        if relaxation not in ("taylor", "exact"):
+            raise ValueError("relaxation must be 'taylor' (the reference's degree-2 polynomial) or 'exact'")
+        if relaxation == "exact" and self.model_mode != "paper":
+            raise ValueError("relaxation='exact' needs model_mode='paper' (reference mode is the reference's "
+                             "code, its Taylor exponential included)")
+
+    def _apply_relaxation(self, relaxation) -> None:
+        N.check(self._lib.tv_set_relaxation(
+            self._ctx, N.TV_RELAX_EXACT if relaxation == "exact" else N.TV_RELAX_TAYLOR), self._ctx)
+
+    def set_relaxation(self, relaxation: str) -> None:
+        """Relaxation factor of the stress update from the next step on: "taylor"
+        (the reference's polynomial) or "exact" (exp / expm1, paper mode only).
+        No field is touched; T, Tf, phi and xi do not depend on it."""
+        self._check_relaxation(relaxation)
+        self._apply_relaxation(relaxation)
+        self.relaxation = relaxation
 
     def num_dofs(self, space=0):
         n = C.c_int64()

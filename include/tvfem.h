@@ -171,7 +171,8 @@ typedef struct {
   int pcg_batch;          /* iterations launched between convergence polls  */
   int pcg_variant;        /* TV_PCG_AUTO / TV_PCG_KSPCG / TV_PCG_SINGLE_REDUCTION */
   int model_mode;         /* TV_MODEL_REFERENCE (default) / TV_MODEL_PAPER /
-                             TV_MODEL_PAPER_EXACT (ensembles only)               */
+                             TV_MODEL_PAPER_EXACT (ensembles only; a single
+                             problem: tv_set_relaxation)                        */
   int preconditioner;     /* TV_PC_JACOBI (default) / TV_PC_GMG (box meshes) /
                              TV_PC_AMG (unstructured meshes, one partition)      */
   int mg_levels;          /* GMG: levels incl. the fine one (0: automatic)       */
@@ -238,11 +239,14 @@ typedef struct {
  * "+" (ViscoelasticModel.py:171), s~ / sigma~ are fed from the previous s /
  * sigma partial stresses (Eq. 16, ViscoelasticModel.py:195-209), and a
  * Dirichlet condition can be applied (tv_set_dirichlet).
- * PAPER_EXACT (ensembles only: tv_ensemble_create_paper; every other
- * constructor returns TV_ERR_ARG) is PAPER with the exponential relaxation
- * itself where both other modes keep the reference's degree-2 Taylor
- * polynomial: E = exp(-x) multiplies the stress memory (Eq. 16) and
- * 1 - E = -expm1(-x) scales the increment (Eq. 15 + 20), x = xi / lambda. */
+ * PAPER_EXACT is PAPER with the exponential relaxation itself where both
+ * other modes keep the reference's degree-2 Taylor polynomial: E = exp(-x)
+ * multiplies the stress memory (Eq. 16) and 1 - E = -expm1(-x) scales the
+ * increment (Eq. 15 + 20), x = xi / lambda.  As a model_mode value it is taken
+ * by tv_ensemble_create_paper only; every other constructor returns
+ * TV_ERR_ARG.  A single-problem context (tv_create, tv_create_unstructured
+ * and their _part forms) is created with TV_MODEL_PAPER and gets the same
+ * relaxation through tv_set_relaxation(ctx, TV_RELAX_EXACT). */
 #define TV_MODEL_REFERENCE 0
 #define TV_MODEL_PAPER 1
 #define TV_MODEL_PAPER_EXACT 2
@@ -366,6 +370,20 @@ int tv_set_initial_condition(void* ctx, double T0);
  * TV_MODEL_PAPER (TV_ERR_STATE otherwise).  DG temperature: no dof belongs to
  * a facet, so the constraint is empty (as locate_dofs_topological would find). */
 int tv_set_dirichlet(void* ctx, int enable, double value);
+/* Relaxation factor of the stress update of a single-problem context (box,
+ * unstructured, slab part, unstructured part).  TAYLOR (the default) is the
+ * reference's polynomial 1 - x + x^2/2, which exceeds 1 for xi > 2 lambda so
+ * that a paper-mode run started above Tb overflows; EXACT is exp(-x) and
+ * -expm1(-x) as TV_MODEL_PAPER_EXACT describes (kernels of their own in
+ * csrc/tv_visco.hip; T, Tf, phi and xi do not depend on it).  It takes effect
+ * from the next viscoelastic update (tv_step, tv_visco_update, tv_time_kernel
+ * id 1) and touches no field.  TV_ERR_ARG for a NULL context or any other
+ * value; TV_RELAX_EXACT on a context whose model_mode is not TV_MODEL_PAPER
+ * returns TV_ERR_STATE and changes nothing; TV_RELAX_TAYLOR is accepted on
+ * every context. */
+#define TV_RELAX_TAYLOR 0
+#define TV_RELAX_EXACT  1
+int tv_set_relaxation(void* ctx, int relaxation);
 int tv_sync(void* ctx);
 
 /* Solver settings after creation: the options in force (tv_get_options), and

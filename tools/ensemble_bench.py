@@ -82,9 +82,9 @@ DG1 / CG1: the setup of --paper except T_0 = 873 K, above Tb, where the Taylor
 form overflows.  In one run the exact ensemble, the same ensemble with
 relaxation="taylor" (its stress overflows at this T_0; the thermal problem and
 the Newton counts do not see it, and only its time is used) and --seq-bars
-(default 1) paper-mode bars through ThermoViscoProblem(model_mode="paper"),
-which has no exact mode: that side runs at main.py's T_0 = 800 K, inside the
-Taylor limit, so that it stays finite over all the steps.  The relaxation moves
+(default 1) bars through ThermoViscoProblem(model_mode="paper",
+relaxation="exact") with the ensemble's own parameters, T_0 = 873 K included:
+the same model on both sides of the ratio.  The relaxation moves
 no byte; per Prony term two exp and two expm1 calls take the place of two
 short polynomials.  The exact / taylor time ratio is recorded,
 not judged; the 64x floor at 4096 bars holds, and the tool exits non-zero below.
@@ -173,8 +173,8 @@ def mode_of(args):
                     baseline_key="taylor_ensemble", baseline_label="taylor", time_ratio="exact_over_taylor_time",
                     bytes_ratio=None, T_0=EXACT_T_0, out="ensemble_exact_bench.json", keyed=True, seq_bars=1,
                     bytes_model="paper mode's (tools/ensemble_bench.py --paper): the relaxation moves no byte",
-                    timed="ThermoViscoProblem {families} model_mode=paper (Taylor; no exact mode exists there) at "
-                          "T_0 = {T_0:g} K, inside the Taylor limit, all {steps} steps: " + timed)
+                    timed="ThermoViscoProblem {families} model_mode=paper relaxation=exact at the ensemble's own "
+                          "T_0 = {T_0:g} K, all {steps} steps: " + timed)
     if args.paper:
         return dict(cell=(fam, "paper"), label=f"paper {FAMILIES[fam]}", baseline=(fam, "reference"),
                     baseline_key="reference_ensemble", baseline_label="reference",
@@ -409,21 +409,21 @@ def bench(args, mode):
         rows.append(row)
         print(line.lstrip(), flush=True)
 
-    # the same work one bar after another (what a parameter study costs without the ensemble).  The
-    # single-problem path has no exact mode: a Taylor paper-mode bar, at main.py's T_0 so that it stays finite
-    seq_wall, seq_total = _time_sequential(mesh, span, CFGS[fam], args.seq_bars, args.steps,
-                                           **(dict(model_mode="paper") if paper else {}))
+    # the same work one bar after another (what a parameter study costs without the ensemble), in the
+    # ensemble's own model and at its own parameters
+    seq_wall, seq_total = _time_sequential(mesh, span, CFGS[fam], args.seq_bars, args.steps, params=params,
+                                           **ENS_KW[model])
     seq_rate = args.seq_bars * args.steps / seq_wall  # the time loops alone: context creation left out
     print(f"sequential {args.seq_bars} {mode['label']} bar(s): ".replace("  ", " ")
           + f"{seq_wall:.3f} s  {seq_rate:.4g} bar-steps/s", flush=True)
     for r in rows:
         r["ratio_to_sequential"] = r["bar_steps_per_s"] / seq_rate
     sequential = {"bars": args.seq_bars, "wall_s": seq_wall, "bar_steps_per_s": seq_rate,
-                  "timed": mode["timed"].format(families=families, T_0=model_params["T_0"], steps=args.steps)}
+                  "timed": mode["timed"].format(families=families, T_0=params["T_0"], steps=args.steps)}
     if base is None:
         sequential["wall_s_with_context_creation"] = seq_total
     if model == "exact":
-        sequential["T_0"] = model_params["T_0"]
+        sequential["T_0"] = params["T_0"]
     res = {"workload": workload, "bytes_model": mode["bytes_model"]}
     if base is not None:
         res["kernel"] = kernel_record(fam, model)
@@ -459,7 +459,7 @@ def main():
                          "its own sequential path")
     ap.add_argument("--exact", action="store_true",
                     help="the exact-relaxation paper ensemble (with --dg: DG1 / CG1) at T_0 = 873 K against the "
-                         "paper-mode ensemble and one sequential paper-mode bar")
+                         "paper-mode ensemble and one sequential exact-relaxation bar")
     args = ap.parse_args()
     if args.scheduled and not (args.paper or args.exact):
         return scheduled_bench(args)
