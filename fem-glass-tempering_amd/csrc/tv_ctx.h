@@ -333,6 +333,40 @@ void op_japply(Ctx* c, const double* T, const double* x, double* y, double* part
 bool op_japply_fused(Ctx* c, const double* T, int* np, const RedTail* tail = nullptr, int it = 0);
 PcgState pcg_state_init(const Ctx* c);
 int ts_flush(Ctx* c);
+// the opening of every Krylov solve: the solve's scalars (pcg_state_init) to
+// the device state; with a gate the solve is skipped on the device (R_SKIPPED)
+void solve_begin(Ctx* c, const double* gate = nullptr);
+// timestamp slot of iteration it of the running solve (see ts_flush), or
+// nullptr: timing off, an untimed stride, slots exhausted, or it < 0
+uint64_t* iter_stamp(const Ctx* c, int it);
+// How one of the five Krylov solves queues its iterations (krylov_drive)
+struct KrylovPolicy {
+  int* hints;         // per Newton index (newton_k): the count that index took in the last step
+  int hint_min;       // the first batch is the hint where the hint exceeds this count ...
+  int first_default;  // ... and this many iterations otherwise
+  int hint_floor;     // the least count written back as a hint (0: a 0-iteration solve leaves none for its index)
+  int init_its;       // leading iterations that are the solve's init: queued on top of the first batch, not counted
+  int next;           // iterations per batch behind the first
+  int guard;          // the solve fails once more iterations than this are queued without convergence
+  int ts_reserve;     // timestamp slots a solve may take (fewer left: ts_flush first)
+  bool ahead;         // batch k + 1 is queued before the host waits for batch k's poll (else: poll, then queue)
+};
+// The queue-and-poll loop of a Krylov solve, behind its init launches:
+// iterate(it, b, nb) queues iteration it, position b of nb in its batch;
+// published() queues what follows a batch's state publish.  Sets *its /
+// *reason, keeps the hints and the timestamp bookkeeping.  The loop is compiled
+// once, in tv_solver.cpp: the template below only hands it the two callables by
+// address (a function pointer and the callable's address each, no allocation).
+using KrylovIterate = int (*)(void* f, int it, int b, int nb);
+using KrylovPublished = int (*)(void* f);
+int krylov_drive(Ctx* c, const KrylovPolicy& p, KrylovIterate iterate, void* fi, KrylovPublished published, void* fp,
+                 int* its, int* reason);
+template <class Iterate, class Published>
+int krylov_drive(Ctx* c, const KrylovPolicy& p, Iterate iterate, Published published, int* its, int* reason) {
+  return krylov_drive(
+      c, p, [](void* f, int it, int b, int nb) -> int { return (*static_cast<Iterate*>(f))(it, b, nb); }, &iterate,
+      [](void* f) -> int { return (*static_cast<Published*>(f))(); }, &published, its, reason);
+}
 CgsBuffers cgs_buffers(Ctx* c, const double* T, int it);
 // step_end (tv_step): 0 none, 1 the visco update, 2 T_prev <- T (thermal only).
 // At the Newton iteration the last step predicts to be the final one, the step's
@@ -357,6 +391,7 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail);
 // post: queue the Newton iteration's post-solve group (launch_post_group, ||dx||
 // copied to h_sums, evn[slot] recorded) behind every batch, gated on the device state
 int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post = false);
+KrylovPolicy mg_krylov_policy(Ctx* c);  // of pcg_solve_mg and the two distributed solves
 bool mg_next_level(const std::vector<double> (&Xp)[3], double da, bool automatic, std::vector<double> (&Xc)[3],
                    std::vector<char> (&is_c)[3], int coarse[3]);
 void mg_axis_tables(const std::vector<double>& Xf, const std::vector<char>& is_c, std::vector<int>& pi,

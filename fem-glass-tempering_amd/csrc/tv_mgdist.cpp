@@ -493,9 +493,7 @@ namespace {
 int mg_iteration_dist(Ctx* c, const double* T, int it, bool fold, bool lag3) {
   int64_t off, n;
   fine_window(c, &off, &n);
-  const int slot = c->ts_next + it;
-  uint64_t* ts = (c->ktime && (it % c->kstride) == 0 && slot < kTsCap) ? c->d_ts + 4 * slot : nullptr;
-  RedTail t1{c->counters, c->partials, c->sums, c->st, 0, ts};
+  RedTail t1{c->counters, c->partials, c->sums, c->st, 0, iter_stamp(c, it)};
   if (lag3) {
     t1.lag = c->sums;
     t1.lag_kind = 3;
@@ -538,9 +536,7 @@ static int pcg_solve_mg_dist_cgs(Ctx* c, const double* T, int* its, int* reason,
   const int64_t off = c->ownT_off, n = c->ownT_n;
   int64_t woff, nwin;
   fine_window(c, &woff, &nwin);
-  const PcgState h = pcg_state_init(c);
-  c->h_st[2] = h;
-  launch_set_state(c->st, h, c->stream, c->solve_gate);
+  solve_begin(c, c->solve_gate);
   if (int e = mg_prepare_dist(c, T)) return e;
   if (c->dir_on)
     if (int e = halo(c, c->dinv)) return e;
@@ -553,9 +549,7 @@ static int pcg_solve_mg_dist_cgs(Ctx* c, const double* T, int* its, int* reason,
   auto half = [&](int it) -> int {
     RedTail tz{c->counters + kTailCounters, c->partials, c->sums, c->st, 0, nullptr};
     if (int e = mg_apply0_dist(c, T, &tz)) return e;
-    const int slot = c->ts_next + it;
-    uint64_t* ts = (it >= 0 && c->ktime && (it % c->kstride) == 0 && slot < kTsCap) ? c->d_ts + 4 * slot : nullptr;
-    RedTail tu{c->counters, c->partials, c->sums + 2, c->st, 0, ts};
+    RedTail tu{c->counters, c->partials, c->sums + 2, c->st, 0, iter_stamp(c, it)};
     if (!launch_cg_japply_tail(c->cg, T, c->z, u, c->st, c->partials, &tu, c->stream))
       return c->fail(TV_ERR_STATE, "single-reduction GMG needs the marching matvec (internal)");
     if (int e = allreduce_halo(c, c->sums, 3, u)) return e;
@@ -563,55 +557,29 @@ static int pcg_solve_mg_dist_cgs(Ctx* c, const double* T, int* its, int* reason,
     return TV_OK;
   };
   if (int e = half(-1)) return e;  // iteration 0's z, u and sums
-  if (c->ktime && c->ts_next + c->O.ksp_max_it + 8 > kTsCap)
-    if (int e = ts_flush(c)) return e;
-  int launched = 0;
-  auto enqueue = [&](int nb) -> int {
-    for (int b = 0; b < nb; ++b) {
-      const int it = launched + b;
-      launch_mg_update_cgs(nwin, c->st, u + woff, c->mg_s + woff, c->z + woff, c->pA + woff, c->f[TV_F_DX].ptr + woff,
-                           c->r + woff, c->dinv + woff, c->mg_omega0, c->mgx + woff, it == 0,
-                           pending ? c->sums : nullptr, pending, c->counters + kUpdateCounter, c->stream);
-      pending = 0;
-      if (int e = half(it)) return e;
-    }
-    launched += nb;
-    if (pending) {  // the host polls the state: the last group's logic as a launch of its own
+  auto iterate = [&](int it, int b, int nb) -> int {
+    launch_mg_update_cgs(nwin, c->st, u + woff, c->mg_s + woff, c->z + woff, c->pA + woff, c->f[TV_F_DX].ptr + woff,
+                         c->r + woff, c->dinv + woff, c->mg_omega0, c->mgx + woff, it == 0,
+                         pending ? c->sums : nullptr, pending, c->counters + kUpdateCounter, c->stream);
+    pending = 0;
+    if (int e = half(it)) return e;
+    if (b + 1 == nb && pending) {  // the host polls the state: the batch's last group's logic as a launch of its own
       launch_logic(c->st, c->sums, pending, c->stream);
       pending = 0;
     }
-    HIPC(hipGetLastError());
-    if (int e = publish(c, &c->h_st[0], c->st, sizeof(PcgState))) return e;
-    HIPC(hipEventRecord(c->evp[0], c->stream));
-    if (post) {  // dx is complete (the updates apply it); the group zeroes it after a 0-iteration solve
-      double* nrm = c->sums + 6;
-      launch_post_group(n, c->st, nullptr, nullptr, c->f[TV_F_DX].ptr + off, c->f[TV_F_T].ptr + off, c->partials, nrm,
-                        c->stream);
-      if (int e = allreduce(c, nrm, 1)) return e;
-      if (int e = queue_newton_norm(c, nrm)) return e;
-    }
     return TV_OK;
   };
-  const int hk = std::min(c->newton_k, 15);
-  if (int e = enqueue(std::max(1, c->mg_hint[hk] > 0 ? c->mg_hint[hk] : c->pcg_hint))) return e;
-  for (;;) {
-    HIPC(hipEventSynchronize(c->evp[0]));
-    if (c->h_st[0].done) break;
-    if (launched > c->O.ksp_max_it + 2) return c->fail(TV_ERR_KSP, "PCG: iteration guard exceeded");
-    if (int e = enqueue(1)) return e;
-  }
-  *its = c->h_st[0].it;
-  *reason = c->h_st[0].reason;
+  auto published = [&]() -> int {
+    if (!post) return TV_OK;
+    // dx is complete (the updates apply it); the group zeroes it after a 0-iteration solve
+    double* nrm = c->sums + 6;
+    launch_post_group(n, c->st, nullptr, nullptr, c->f[TV_F_DX].ptr + off, c->f[TV_F_T].ptr + off, c->partials, nrm,
+                      c->stream);
+    if (int e = allreduce(c, nrm, 1)) return e;
+    return queue_newton_norm(c, nrm);
+  };
+  if (int e = krylov_drive(c, mg_krylov_policy(c), iterate, published, its, reason)) return e;
   if (!post && *its == 0) launch_fill(c->f[TV_F_DX].ptr + off, n, 0.0, c->stream);
-  if (*reason != R_SKIPPED) {  // a solve gated off by the Newton test says nothing of the count
-    c->pcg_hint = std::max(1, c->h_st[0].it);
-    c->mg_hint[hk] = c->pcg_hint;
-  }
-  if (c->ktime) {
-    for (int it = 0; it < *its; it += c->kstride)
-      if (c->ts_next + it < kTsCap) c->ts_pending.push_back(c->ts_next + it);
-    c->ts_next = std::min(kTsCap, c->ts_next + launched);
-  }
   return TV_OK;
 }
 
@@ -620,9 +588,7 @@ int pcg_solve_mg_dist(Ctx* c, const double* T, int* its, int* reason, bool post)
   const int64_t off = c->ownT_off, n = c->ownT_n;
   int64_t woff, nwin;
   fine_window(c, &woff, &nwin);
-  const PcgState h = pcg_state_init(c);
-  c->h_st[2] = h;
-  launch_set_state(c->st, h, c->stream, c->solve_gate);
+  solve_begin(c, c->solve_gate);
   if (c->amg_on) {  // the algebraic hierarchy is T-independent; level 0's weight at the first solve
     if (int e = mg_dg_weight(c, T)) return e;
   } else if (int e = mg_prepare_dist(c, T)) {
@@ -661,52 +627,23 @@ int pcg_solve_mg_dist(Ctx* c, const double* T, int* its, int* reason, bool post)
     if (int e = mg_apply0_dist(c, T, &t0)) return e;
     if (int e = close(1, false)) return e;  // dp, beta (KSPCG init)
   }
-  if (c->ktime && c->ts_next + c->O.ksp_max_it + 8 > kTsCap)
-    if (int e = ts_flush(c)) return e;
-  // queued as in pcg_solve_mg: the previous solve's count behind the init, then
-  // one iteration per poll.  Every rank takes the same decisions: the polled
-  // state is formed from all-reduced sums, identical on every rank.
-  int launched = 0;
-  auto enqueue = [&](int nb) -> int {
-    for (int b = 0; b < nb; ++b) {
-      if (int e = mg_iteration_dist(c, T, launched + b, fold, lag3)) return e;
-      // z.z, z.r -> beta, convergence: lagged into the next iteration's fused
-      // matvec, except after the batch's last iteration (the host polls the state)
-      if (int e = close(3, fold && b + 1 < nb)) return e;
-    }
-    launched += nb;
-    HIPC(hipGetLastError());
-    if (int e = publish(c, &c->h_st[0], c->st, sizeof(PcgState))) return e;
-    HIPC(hipEventRecord(c->evp[0], c->stream));
-    if (post) {  // the Newton iteration's next work, gated on the (all-reduced, rank-identical) state
-      double* nrm = c->sums + 6;  // not c->sums: the lagged logic reads those across the batch boundary
-      launch_post_group(n, c->st, c->pA + off, c->pB + off, c->f[TV_F_DX].ptr + off, c->f[TV_F_T].ptr + off,
-                        c->partials, nrm, c->stream);
-      if (int e = allreduce(c, nrm, 1)) return e;  // collective on every rank, run or gated off
-      if (int e = queue_newton_norm(c, nrm)) return e;
-    }
-    return TV_OK;
+  auto iterate = [&](int it, int b, int nb) -> int {
+    if (int e = mg_iteration_dist(c, T, it, fold, lag3)) return e;
+    // z.z, z.r -> beta, convergence: lagged into the next iteration's fused
+    // matvec, except after the batch's last iteration (the host polls the state)
+    return close(3, fold && b + 1 < nb);
   };
-  const int hk = std::min(c->newton_k, 15);  // every rank polls the same all-reduced state: same decisions
-  if (int e = enqueue(std::max(1, c->mg_hint[hk] > 0 ? c->mg_hint[hk] : c->pcg_hint))) return e;
-  for (;;) {
-    HIPC(hipEventSynchronize(c->evp[0]));
-    if (c->h_st[0].done) break;
-    if (launched > c->O.ksp_max_it + 2) return c->fail(TV_ERR_KSP, "PCG: iteration guard exceeded");
-    if (int e = enqueue(1)) return e;
-  }
-  *its = c->h_st[0].it;
-  *reason = c->h_st[0].reason;
+  auto published = [&]() -> int {
+    if (!post) return TV_OK;
+    // the Newton iteration's next work, gated on the (all-reduced, rank-identical) state
+    double* nrm = c->sums + 6;  // not c->sums: the lagged logic reads those across the batch boundary
+    launch_post_group(n, c->st, c->pA + off, c->pB + off, c->f[TV_F_DX].ptr + off, c->f[TV_F_T].ptr + off,
+                      c->partials, nrm, c->stream);
+    if (int e = allreduce(c, nrm, 1)) return e;  // collective on every rank, run or gated off
+    return queue_newton_norm(c, nrm);
+  };
+  if (int e = krylov_drive(c, mg_krylov_policy(c), iterate, published, its, reason)) return e;
   if (!post) launch_mg_dx_finish(n, c->st, c->pA + off, c->pB + off, c->f[TV_F_DX].ptr + off, *its, c->stream);
-  if (*reason != R_SKIPPED) {  // a solve gated off by the Newton test says nothing of the count
-    c->pcg_hint = std::max(1, c->h_st[0].it);
-    c->mg_hint[hk] = c->pcg_hint;
-  }
-  if (c->ktime) {
-    for (int it = 0; it < *its; it += c->kstride)
-      if (c->ts_next + it < kTsCap) c->ts_pending.push_back(c->ts_next + it);
-    c->ts_next = std::min(kTsCap, c->ts_next + launched);
-  }
   return TV_OK;
 }
 

@@ -568,9 +568,7 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
 
 int mg_iteration(Ctx* c, const double* T, int it) {
   const int64_t n = c->nT;
-  const int slot = c->ts_next + it;
-  uint64_t* ts = (c->ktime && (it % c->kstride) == 0 && slot < kTsCap) ? c->d_ts + 4 * slot : nullptr;
-  RedTail t1{c->counters, c->partials, c->sums, c->st, 2, ts};
+  RedTail t1{c->counters, c->partials, c->sums, c->st, 2, iter_stamp(c, it)};
   int np = 0;
   if (!op_japply_fused(c, T, &np, &t1, it))  // p <- z + b p ; w <- J p ; p.w ; alpha
     if (int e = reduce_logic(c, np, 1, 2, 1)) return e;
@@ -586,13 +584,30 @@ int mg_iteration(Ctx* c, const double* T, int it) {
   return nrec < 0 ? -nrec : TV_OK;
 }
 
+// The three multigrid solves queue alike.  An MG iteration is ~25 launches: the
+// count this Newton index took in the last step (hint) is queued right behind
+// the init, with no host wait in between (the GPU would idle while the host
+// enqueues ~100 launches), then one iteration at a time behind a poll.  The
+// Newton solves of a step take near-constant counts, so the hint usually ends
+// the solve at the first poll.  On several ranks every rank takes the same
+// decisions: the polled state is formed from all-reduced sums, identical on
+// every rank.
+KrylovPolicy mg_krylov_policy(Ctx* c) {
+  KrylovPolicy p{};
+  p.ahead = false;
+  p.hints = c->mg_hint;
+  p.hint_min = 0;
+  p.first_default = 1;
+  p.hint_floor = 1;
+  p.next = 1;
+  p.guard = c->O.ksp_max_it + 2;
+  p.ts_reserve = c->O.ksp_max_it + 8;
+  return p;
+}
+
 int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
   const int64_t n = c->nT;
-  const PcgState h = pcg_state_init(c);
-  // from pinned memory (an asynchronous upload; a pageable source is staged by
-  // the runtime -- no step-time change measured at C2 / C3 / C4)
-  c->h_st[2] = h;
-  launch_set_state(c->st, h, c->stream, c->solve_gate);
+  solve_begin(c, c->solve_gate);
   if (int e = mg_prepare(c, T)) return e;
   if (int e = mg_dg_weight(c, T)) return e;
   if (c->dggface)
@@ -603,50 +618,17 @@ int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
                      c->stream);  // dx <- 0, x0 <- omega dinv r
   RedTail t0{c->counters + kTailCounters, c->partials, c->sums, c->st, 1, nullptr};
   if (const int nrec = mg_apply0(c, T, &t0); nrec < 0) return -nrec;  // z <- V(r); dp, beta (KSPCG init)
-  if (c->ktime && c->ts_next + c->O.ksp_max_it + 8 > kTsCap)
-    if (int e = ts_flush(c)) return e;
-  // an MG iteration is ~25 launches: the previous solve's count (hint) is queued
-  // right behind the init, with no host wait in between (the GPU would idle
-  // while the host enqueues ~100 launches; an init that already converged
-  // makes every queued launch exit at once), then one iteration at a time
-  // behind a poll.  The Newton solves of a step take near-constant counts, so
-  // the hint usually ends the solve at the first poll.
-  int launched = 0;
-  auto enqueue = [&](int nb) -> int {
-    for (int b = 0; b < nb; ++b)
-      if (int e = mg_iteration(c, T, launched + b)) return e;
-    launched += nb;
-    HIPC(hipGetLastError());
-    if (int e = publish(c, &c->h_st[0], c->st, sizeof(PcgState))) return e;
-    HIPC(hipEventRecord(c->evp[0], c->stream));
-    if (post) {  // the Newton iteration's next work, queued before the host's poll (it runs once)
-      launch_post_group(n, c->st, c->pA, c->pB, c->f[TV_F_DX].ptr, c->f[TV_F_T].ptr, c->partials, c->sums, c->stream);
-      if (int e = queue_newton_norm(c, c->sums)) return e;
-    }
-    return TV_OK;
+  auto iterate = [&](int it, int, int) { return mg_iteration(c, T, it); };
+  auto published = [&]() -> int {
+    if (!post) return TV_OK;
+    // the Newton iteration's next work, queued before the host's poll (it runs once)
+    launch_post_group(n, c->st, c->pA, c->pB, c->f[TV_F_DX].ptr, c->f[TV_F_T].ptr, c->partials, c->sums, c->stream);
+    return queue_newton_norm(c, c->sums);
   };
-  const int hk = std::min(c->newton_k, 15);
-  if (int e = enqueue(std::max(1, c->mg_hint[hk] > 0 ? c->mg_hint[hk] : c->pcg_hint))) return e;
-  for (;;) {
-    HIPC(hipEventSynchronize(c->evp[0]));
-    if (c->h_st[0].done) break;
-    if (launched > c->O.ksp_max_it + 2) return c->fail(TV_ERR_KSP, "PCG: iteration guard exceeded");
-    if (int e = enqueue(1)) return e;
-  }
-  *its = c->h_st[0].it;
-  *reason = c->h_st[0].reason;
+  if (int e = krylov_drive(c, mg_krylov_policy(c), iterate, published, its, reason)) return e;
   // level 0 updates dx in pairs of iterations from iteration 1 on (k_mg_update /
   // k_dg_bupdate DXU): solves of 0 / 1 iterations and the last step of an odd-length one
   if (!post) launch_mg_dx_finish(n, c->st, c->pA, c->pB, c->f[TV_F_DX].ptr, *its, c->stream);
-  if (*reason != R_SKIPPED) {  // a solve gated off by the Newton test says nothing of the count
-    c->pcg_hint = std::max(1, c->h_st[0].it);
-    c->mg_hint[hk] = c->pcg_hint;
-  }
-  if (c->ktime) {
-    for (int it = 0; it < *its; it += c->kstride)
-      if (c->ts_next + it < kTsCap) c->ts_pending.push_back(c->ts_next + it);
-    c->ts_next = std::min(kTsCap, c->ts_next + launched);
-  }
   return TV_OK;
 }
 

@@ -1,8 +1,12 @@
 // The Newton + Krylov drivers of the heat solve and the viscoelastic step.
 //   newton               dolfinx NewtonSolver::solve, incremental criterion,
 //                        configured at ThermoViscoProblem.py:330-346 [3P]
-//   pcg_solve            PETSc KSPSolve_CG + PCJACOBI restated on the device
-//   pcg_solve_cgs        the single-reduction (Chronopoulos-Gear) form
+//   krylov_drive         the queue-and-poll loop of the five Krylov solves:
+//     pcg_solve              PETSc KSPSolve_CG + PCJACOBI restated on the device (here)
+//     pcg_solve_cgs          its single-reduction (Chronopoulos-Gear) form (here)
+//     pcg_solve_mg           GMG / AMG preconditioned, one partition (tv_mgsolve.cpp)
+//     pcg_solve_mg_dist      distributed GMG, KSPCG form (tv_mgdist.cpp)
+//     pcg_solve_mg_dist_cgs  distributed GMG, single-reduction form (tv_mgdist.cpp)
 //   visco                _solve_Tf .. _solve_stress (ThermoViscoProblem.py:393-595)
 #include <cstdlib>
 
@@ -47,7 +51,6 @@ bool op_japply_fused(Ctx* c, const double* T, int* np, const RedTail* tail, int 
 // it: index of this iteration within the solve (the device counter st->it
 // equals it until convergence, after which every kernel exits at once)
 
-// reads the pending timestamp slots back and adds them to the stats
 // the scalars of a Krylov solve at its start (PETSc KSPSetTolerances); with
 // ksp_fixed_its the solve runs exactly that many iterations (no convergence
 // test: KSP_NORM_NONE), which newton() accepts
@@ -68,6 +71,15 @@ PcgState pcg_state_init(const Ctx* c) {
   return h;
 }
 
+void solve_begin(Ctx* c, const double* gate) {
+  const PcgState h = pcg_state_init(c);
+  // from pinned memory (an asynchronous upload; a pageable source is staged by
+  // the runtime -- no step-time change measured at C2 / C3 / C4)
+  c->h_st[2] = h;
+  launch_set_state(c->st, h, c->stream, gate);
+}
+
+// reads the pending timestamp slots back and adds them to the stats
 int ts_flush(Ctx* c) {
   if (!c->d_ts) return TV_OK;
   if (!c->ts_pending.empty()) {
@@ -89,16 +101,74 @@ int ts_flush(Ctx* c) {
   return TV_OK;
 }
 
+uint64_t* iter_stamp(const Ctx* c, int it) {
+  const int slot = c->ts_next + it;
+  return (it >= 0 && c->ktime && (it % c->kstride) == 0 && slot < kTsCap) ? c->d_ts + 4 * slot : nullptr;
+}
+
+// The first batch goes into the stream right behind the solve's init, with no
+// host wait in between; an init that already converged (or a solve gated off)
+// makes every queued launch exit at its first instruction.  Each batch ends
+// with the device state published to a pinned slot and an event, which the
+// host polls.  Two disciplines (KrylovPolicy::ahead):
+//   ahead   batches are queued one ahead of the convergence poll: while the
+//           host waits for the state copied at the end of batch k, batch k + 1
+//           is already in the stream (slots / events k & 1), so the GPU never
+//           idles on the host's turnaround.  The batch queued behind the
+//           converged one exits early; stream order covers it.
+//   else    poll, then queue the next batch (slot 0 only).
+// The first batch is sized by the count this Newton index took in the last
+// step (the counts repeat from step to step, and decrease along a step's Newton
+// iterations, so the previous solve's count -- pcg_hint, the fallback for an
+// index not seen yet -- over-queues).  hipGetLastError is checked once per batch.
+int krylov_drive(Ctx* c, const KrylovPolicy& p, KrylovIterate iterate, void* fi, KrylovPublished published, void* fp,
+                 int* its, int* reason) {
+  if (c->ktime && c->ts_next + p.ts_reserve > kTsCap)
+    if (int e = ts_flush(c)) return e;
+  int launched = 0;
+  auto enqueue = [&](int nb, int k) -> int {
+    for (int b = 0; b < nb; ++b)
+      if (int e = iterate(fi, launched + b, b, nb)) return e;
+    launched += nb;
+    HIPC(hipGetLastError());
+    if (int e = publish(c, &c->h_st[k], c->st, sizeof(PcgState))) return e;
+    HIPC(hipEventRecord(c->evp[k], c->stream));
+    return published(fp);
+  };
+  const int hk = std::min(c->newton_k, 15);
+  const int hint = p.hints[hk] > 0 ? p.hints[hk] : c->pcg_hint;
+  if (int e = enqueue(p.init_its + (hint > p.hint_min ? hint : p.first_default), 0)) return e;
+  int slot = 0;
+  for (;;) {
+    if (p.ahead)
+      if (int e = enqueue(p.next, slot ^ 1)) return e;
+    HIPC(hipEventSynchronize(c->evp[slot]));
+    if (c->h_st[slot].done) break;
+    if (launched > p.guard) return c->fail(TV_ERR_KSP, "PCG: iteration guard exceeded");
+    if (p.ahead) slot ^= 1;
+    else if (int e = enqueue(p.next, 0)) return e;
+  }
+  *its = c->h_st[slot].it;
+  *reason = c->h_st[slot].reason;
+  // a solve gated off by the Newton test says nothing of the count (only the
+  // multigrid solves are gated)
+  if (*reason != R_SKIPPED) c->pcg_hint = p.hints[hk] = std::max(p.hint_floor, *its);
+  if (c->ktime) {  // productive iterations only (launches queued behind convergence exit at once)
+    for (int it = p.init_its; it < p.init_its + *its; it += c->kstride)
+      if (c->ts_next + it < kTsCap) c->ts_pending.push_back(c->ts_next + it);
+    c->ts_next = std::min(kTsCap, c->ts_next + launched);
+  }
+  return TV_OK;
+}
+
 // lag3: the beta / convergence logic of the previous closing group runs lagged
 // inside this iteration's fused matvec (box march only); defer3: this
 // iteration's closing logic is left to the next one the same way.  The alpha
 // logic of a multi-rank iteration runs lagged inside the update.
 int pcg_iteration(Ctx* c, const double* T, int it, bool lag3, bool defer3) {
   const int64_t off = c->ownT_off, n = c->ownT_n;
-  // timestamp slot of this iteration (see ts_flush); the matvec launchers
-  // without a reduction tail (DG, 1D/2D CG) leave theirs at 0
-  const int slot = c->ts_next + it;
-  uint64_t* ts = (c->ktime && (it % c->kstride) == 0 && slot < kTsCap) ? c->d_ts + 4 * slot : nullptr;
+  // the matvec launchers without a reduction tail (DG, 1D/2D CG) leave their stamps at 0
+  uint64_t* ts = iter_stamp(c, it);
   const bool multi = multi_rank(c);
   // single GPU: the last-arriving workgroup of each launch reduces the partial
   // records and runs the KSPCG scalar logic in-kernel (no separate reduce
@@ -131,63 +201,30 @@ int pcg_iteration(Ctx* c, const double* T, int it, bool lag3, bool defer3) {
 
 int pcg_solve(Ctx* c, const double* T, int* its, int* reason) {
   const int64_t off = c->ownT_off, n = c->ownT_n;
-  // state init
-  const PcgState h = pcg_state_init(c);
-  // from pinned memory (an asynchronous upload; a pageable source is staged by
-  // the runtime -- no step-time change measured at C2 / C3 / C4)
-  c->h_st[2] = h;
-  launch_set_state(c->st, h, c->stream);
+  solve_begin(c);
   launch_pcg_init(n, c->r + off, c->dinv + off, c->z + off, c->f[TV_F_DX].ptr + off, c->partials, c->stream);
   if (int e = reduce_logic(c, pcg_vec_blocks(n), 2, 1, 0)) return e;
   if (int e = halo(c, c->z)) return e;
-  if (c->ktime && c->ts_next + c->O.ksp_max_it + 4 * c->O.pcg_batch + 8 > kTsCap)
-    if (int e = ts_flush(c)) return e;
-  // Batches of iterations are queued one ahead of the convergence poll: while
-  // the host waits for the state copied at the end of batch k, batch k + 1 is
-  // already in the stream, so the GPU never idles on the host's turnaround.
-  // After convergence the queued launches exit at their first instruction.
-  int launched = 0, slot = 0;
-  // multi-rank box march: the closing logic of an iteration runs lagged in the
-  // next one's fused matvec, except after a batch's last iteration (polled)
-  const bool fold = multi_rank(c) && !c->um && c->fam_T == TV_CG && cg_cgs_supported(c->cg);
-  auto enqueue = [&](int nb, int k) -> int {
-    for (int b = 0; b < nb; ++b)
-      if (int e = pcg_iteration(c, T, launched + b, fold && b > 0, fold && b + 1 < nb)) return e;
-    launched += nb;
-    HIPC(hipGetLastError());
-    if (int e = publish(c, &c->h_st[k], c->st, sizeof(PcgState))) return e;
-    HIPC(hipEventRecord(c->evp[k], c->stream));
-    return TV_OK;
-  };
+  KrylovPolicy p{};
+  p.ahead = true;
+  // first batch: this Newton index's count in the last step (measured: previous
+  // count - 3 C2 0.97-0.99 ms, this index's count - 1 0.90-0.92, its count
+  // 0.88-0.89); a hint of 4 or less gives way to pcg_batch
+  p.hints = c->jac_hint;
+  p.hint_min = 4;
+  p.first_default = std::max(1, c->O.pcg_batch);
   // batches queued behind the first: pcg_batch / 8 iterations (1 by default);
   // the host's turnaround (~30 us) is well inside one iteration (~130 us at C4),
   // and every iteration queued past convergence costs two early-exit launches
-  const int small = std::max(1, c->O.pcg_batch / 8);
-  // first batch: the count this Newton index took in the last step (the counts
-  // repeat from step to step, and decrease along a step's Newton iterations,
-  // so the previous solve's count over-queues; measured: previous count - 3
-  // C2 0.97-0.99 ms, this index's count - 1 0.90-0.92, its count 0.88-0.89)
-  const int hk = std::min(c->newton_k, 15);
-  const int hint = c->jac_hint[hk] > 0 ? c->jac_hint[hk] : c->pcg_hint;
-  if (int e = enqueue(std::max(1, hint > 4 ? hint : c->O.pcg_batch), 0)) return e;
-  for (;;) {
-    if (int e = enqueue(small, slot ^ 1)) return e;
-    HIPC(hipEventSynchronize(c->evp[slot]));
-    if (c->h_st[slot].done) break;
-    if (launched > c->O.ksp_max_it + 2 * small + 2) return c->fail(TV_ERR_KSP, "PCG: iteration guard exceeded");
-    slot ^= 1;
-  }
-  // (the batch queued behind the converged one exits early; stream order covers it)
-  *its = c->h_st[slot].it;
-  *reason = c->h_st[slot].reason;
+  p.next = std::max(1, c->O.pcg_batch / 8);
+  p.guard = c->O.ksp_max_it + 2 * p.next + 2;
+  p.ts_reserve = c->O.ksp_max_it + 4 * c->O.pcg_batch + 8;
+  // multi-rank box march: the closing logic of an iteration runs lagged in the
+  // next one's fused matvec, except after a batch's last iteration (polled)
+  const bool fold = multi_rank(c) && !c->um && c->fam_T == TV_CG && cg_cgs_supported(c->cg);
+  auto iterate = [&](int it, int b, int nb) { return pcg_iteration(c, T, it, fold && b > 0, fold && b + 1 < nb); };
+  if (int e = krylov_drive(c, p, iterate, [] { return TV_OK; }, its, reason)) return e;
   launch_pcg_dx_tail(n, c->st, c->pA + off, c->pB + off, c->f[TV_F_DX].ptr + off, *its, c->stream);
-  c->pcg_hint = c->h_st[slot].it;
-  c->jac_hint[hk] = c->pcg_hint;
-  if (c->ktime) {  // productive iterations only (launches queued behind convergence exit at once)
-    for (int it = 0; it < *its; it += c->kstride)
-      if (c->ts_next + it < kTsCap) c->ts_pending.push_back(c->ts_next + it);
-    c->ts_next = std::min(kTsCap, c->ts_next + launched);
-  }
   return TV_OK;
 }
 
@@ -214,10 +251,8 @@ CgsBuffers cgs_buffers(Ctx* c, const double* T, int it) {
 
 int cgs_iteration(Ctx* c, const double* T, int it) {
   const bool multi = multi_rank(c);
-  const int slot = c->ts_next + it;
-  uint64_t* ts = (c->ktime && (it % c->kstride) == 0 && slot < kTsCap) ? c->d_ts + 4 * slot : nullptr;
   const int kind = multi ? 0 : (it == 0 ? 4 : 5);
-  RedTail rt{c->counters, c->partials, c->sums, c->st, kind, ts};
+  RedTail rt{c->counters, c->partials, c->sums, c->st, kind, iter_stamp(c, it)};
   const CgsBuffers v = cgs_buffers(c, T, it);
   launch_cg_cgs(c->cg, it == 0, v, c->st, c->partials, c->stream, &rt, it, (multi && it > 0) ? c->sums : nullptr);
   if (multi)
@@ -226,50 +261,24 @@ int cgs_iteration(Ctx* c, const double* T, int it) {
 }
 
 int pcg_solve_cgs(Ctx* c, const double* T, int* its, int* reason) {
-  const PcgState h = pcg_state_init(c);
-  // from pinned memory (an asynchronous upload; a pageable source is staged by
-  // the runtime -- no step-time change measured at C2 / C3 / C4)
-  c->h_st[2] = h;
-  launch_set_state(c->st, h, c->stream);
+  solve_begin(c);
   // ghost planes of r_0 and diag^-1 (the halo rows recompute z there)
   if (int e = halo(c, c->r)) return e;
   if (int e = halo(c, c->dinv)) return e;
-  if (c->ktime && c->ts_next + c->O.ksp_max_it + 4 * c->O.pcg_batch + 8 > kTsCap)
-    if (int e = ts_flush(c)) return e;
-  int launched = 0, slot = 0;
-  auto enqueue = [&](int nb, int k) -> int {
-    for (int b = 0; b < nb; ++b)
-      if (int e = cgs_iteration(c, T, launched + b)) return e;
-    launched += nb;
-    HIPC(hipGetLastError());
-    if (int e = publish(c, &c->h_st[k], c->st, sizeof(PcgState))) return e;
-    HIPC(hipEventRecord(c->evp[k], c->stream));
-    return TV_OK;
-  };
-  // iteration 0 and the first batch, then one more iteration queued behind
-  // every poll (see pcg_solve); multi-rank the state lags one launch
-  const int lag = multi_rank(c) ? 1 : 0;
-  const int small = 1 + lag;
-  const int hk = std::min(c->newton_k, 15);  // as pcg_solve: this Newton index's count in the last step
-  const int hint = c->jac_hint[hk] > 0 ? c->jac_hint[hk] : c->pcg_hint;
-  if (int e = enqueue(1 + std::max(1, hint > 4 ? hint : c->O.pcg_batch), 0)) return e;
-  for (;;) {
-    if (int e = enqueue(small, slot ^ 1)) return e;
-    HIPC(hipEventSynchronize(c->evp[slot]));
-    if (c->h_st[slot].done) break;
-    if (launched > c->O.ksp_max_it + 2 * small + 4) return c->fail(TV_ERR_KSP, "PCG: iteration guard exceeded");
-    slot ^= 1;
-  }
-  *its = c->h_st[slot].it;
-  *reason = c->h_st[slot].reason;
-  c->pcg_hint = *its;
-  c->jac_hint[hk] = *its;
-  if (c->ktime) {
-    for (int it = 1; it <= *its; it += c->kstride)  // productive iterations (iteration 0 is the init launch)
-      if (c->ts_next + it < kTsCap) c->ts_pending.push_back(c->ts_next + it);
-    c->ts_next = std::min(kTsCap, c->ts_next + launched);
-  }
-  return TV_OK;
+  // as pcg_solve, but iteration 0 is the init launch: it goes with the first
+  // batch, then one more iteration is queued behind every poll; multi-rank the
+  // state lags one launch
+  KrylovPolicy p{};
+  p.ahead = true;
+  p.hints = c->jac_hint;
+  p.hint_min = 4;
+  p.first_default = std::max(1, c->O.pcg_batch);
+  p.init_its = 1;
+  p.next = 1 + (multi_rank(c) ? 1 : 0);
+  p.guard = c->O.ksp_max_it + 2 * p.next + 4;
+  p.ts_reserve = c->O.ksp_max_it + 4 * c->O.pcg_batch + 8;
+  auto iterate = [&](int it, int, int) { return cgs_iteration(c, T, it); };
+  return krylov_drive(c, p, iterate, [] { return TV_OK; }, its, reason);
 }
 
 const char* reason_str(int r) {
