@@ -498,7 +498,8 @@ int setup_fields(Ctx* c) {
   c->f[TV_F_RESIDUAL].ptr = c->r; c->f[TV_F_RESIDUAL].bs = 1; c->f[TV_F_RESIDUAL].space = 0;
   if (int e = alloc_field(c, TV_F_DX, 0, 1)) return e;
   int np = kVecBlocksMax;
-  if (c->um) np = std::max(np, um_num_blocks(c->umg));
+  if (c->um_dg) np = std::max(np, umdg_num_blocks(c->udg));
+  else if (c->um) np = std::max(np, um_num_blocks(c->umg));
   else if (c->fam_T == TV_CG) np = std::max(np, cg_num_blocks(c->cg, true));
   else np = std::max(np, dg_num_blocks(c->dg));
   c->n_partials_cap = np;
@@ -758,8 +759,16 @@ int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params*
 static int setup_umesh(Ctx* c, const tv_umesh_desc* m, const tv_upart_desc* pd) {
   const int d = m->dim;
   if (d != 2 && d != 3) return c->fail(TV_ERR_ARG, "unstructured meshes: dim 2 (quadrilaterals) or 3 (hexahedra)");
-  if (c->fam_T != TV_CG || c->fam_S != TV_CG)
-    return c->fail(TV_ERR_ARG, "unstructured meshes: CG temperature and stress spaces only");
+  if ((c->fam_T != TV_CG && c->fam_T != TV_DG) || (c->fam_S != TV_CG && c->fam_S != TV_DG))
+    return c->fail(TV_ERR_ARG, "unstructured meshes: only CG and DG elements are supported");
+  const bool any_dg = c->fam_T == TV_DG || c->fam_S == TV_DG;
+  if (pd && any_dg)
+    return c->fail(TV_ERR_ARG, "tv_create_unstructured_part: CG temperature and stress spaces only (a partition's "
+                               "ghost layer carries vertex dofs; DG cell dofs on partitioned unstructured meshes "
+                               "are not implemented)");
+  if (c->fam_T == TV_DG && c->O.preconditioner == TV_PC_AMG)
+    return c->fail(TV_ERR_ARG, "unstructured meshes: TV_PC_AMG needs a CG temperature space (the aggregation works "
+                               "on the vertex operator; DG temperature takes TV_PC_JACOBI)");
   if (m->n_vertices < 1 || m->n_cells < 1 || !m->coords || !m->cells) return c->fail(TV_ERR_ARG, "empty mesh");
   if (m->n_vertices >= INT32_MAX) return c->fail(TV_ERR_ARG, "unstructured meshes: < 2^31 vertices");
   const int nl = 1 << d;
@@ -813,16 +822,43 @@ static int setup_umesh(Ctx* c, const tv_umesh_desc* m, const tv_upart_desc* pd) 
   g.a_rad = 0.001 * (P.sigma * P.epsilon); g.a_conv = 0.001 * P.htc;
   g.T_amb = P.T_ambient; g.T_amb4 = P.T_ambient * P.T_ambient * P.T_ambient * P.T_ambient;
   std::string err;
-  if (um_setup(d, m->n_vertices, nown, m->coords, m->n_cells, m->cells, g, c->umd, c->stream, err) != 0)
-    return c->fail(err.rfind("HIP", 0) == 0 ? TV_ERR_HIP : TV_ERR_ARG, err);
-  std::vector<unsigned char> bm;
-  um_boundary_vertices(c->umd, bm);
-  HIPC(tv_dev_alloc(&c->um_bmask, bm.size(), kMemOther));
-  HIPC(hipMemcpy(c->um_bmask, bm.data(), bm.size(), hipMemcpyHostToDevice));
-  c->nT = c->nS = g.nv;
+  const int64_t ndg = m->n_cells * nl;  // DG dofs: device layout [l][cell], host layout cell-major
+  if (any_dg && ndg >= (int64_t)INT32_MAX) return c->fail(TV_ERR_ARG, "unstructured meshes: < 2^31 DG dofs");
+  if (c->fam_T == TV_DG) {  // the SIPG operator on cell blocks (tv_umdg.hip); nothing on vertex dofs is built
+    c->um_dg = true;
+    c->udg.rb = g;  // the thermal constants
+    if (umdg_setup(d, m->n_vertices, m->coords, m->n_cells, m->cells, c->udg, c->udgd, c->stream, err) != 0)
+      return c->fail(err.rfind("HIP", 0) == 0 ? TV_ERR_HIP : TV_ERR_ARG, err);
+    c->nT = c->ownT_n = ndg;
+  } else {
+    if (um_setup(d, m->n_vertices, nown, m->coords, m->n_cells, m->cells, g, c->umd, c->stream, err) != 0)
+      return c->fail(err.rfind("HIP", 0) == 0 ? TV_ERR_HIP : TV_ERR_ARG, err);
+    std::vector<unsigned char> bm;
+    um_boundary_vertices(c->umd, bm);
+    HIPC(tv_dev_alloc(&c->um_bmask, bm.size(), kMemOther));
+    HIPC(hipMemcpy(c->um_bmask, bm.data(), bm.size(), hipMemcpyHostToDevice));
+    c->nT = g.nv;
+    c->ownT_n = nown;
+  }
+  c->nS = c->fam_S == TV_DG ? ndg : m->n_vertices;
+  c->ownS_n = c->fam_S == TV_DG ? ndg : nown;
   c->ownT_off = c->ownS_off = 0;
-  c->ownT_n = c->ownS_n = nown;
   c->globT_off = c->globS_off = pd ? pd->global_offset : 0;
+  if (c->fam_T != c->fam_S) {
+    // fem::interpolate between the families: cells in order, the last cell
+    // written wins at a shared vertex (as setup_mesh does for boxes)
+    std::vector<int> map((size_t)c->nS, -1);
+    for (int64_t e = 0; e < m->n_cells; ++e)
+      for (int l = 0; l < nl; ++l) {
+        const int64_t v = m->cells[e * nl + l], dg = (int64_t)l * m->n_cells + e;
+        if (c->fam_S == TV_CG) map[(size_t)v] = (int)dg;  // sigma CG <- T DG
+        else map[(size_t)dg] = (int)v;                    // sigma DG <- T CG
+      }
+    for (int64_t k = 0; k < c->nS; ++k)
+      if (map[(size_t)k] < 0) return c->fail(TV_ERR_ARG, "unstructured meshes: a vertex that belongs to no cell");
+    HIPC(tv_dev_alloc(&c->map, sizeof(int) * (size_t)c->nS, kMemOther));
+    HIPC(hipMemcpy(c->map, map.data(), sizeof(int) * (size_t)c->nS, hipMemcpyHostToDevice));
+  }
   return TV_OK;
 }
 
@@ -919,6 +955,26 @@ int tv_partition_rcb(const tv_umesh_desc* m, int n_parts, int* part_out) {
 }
 
 
+int tv_um_facets(const tv_umesh_desc* m, int64_t* n_interior, int64_t* interior5, int64_t* n_exterior,
+                 int64_t* exterior2) {
+  if (!m || !m->cells || (m->dim != 2 && m->dim != 3)) {
+    set_global_error("tv_um_facets: bad argument");
+    return TV_ERR_ARG;
+  }
+  std::vector<int64_t> ext, in;
+  std::string err;
+  if (um_facets(m->dim, m->n_vertices, m->n_cells, m->cells, ext, in, err)) {
+    set_global_error(err);
+    return TV_ERR_ARG;
+  }
+  if (n_interior) *n_interior = (int64_t)in.size() / 5;
+  if (n_exterior) *n_exterior = (int64_t)ext.size() / 2;
+  if (interior5) std::copy(in.begin(), in.end(), interior5);
+  if (exterior2) std::copy(ext.begin(), ext.end(), exterior2);
+  return TV_OK;
+}
+
+
 int tv_partition_layout(const tv_mesh_desc* m, int64_t* out) {
   if (!m || !out || m->dim < 1 || m->dim > 3 || m->n_parts < 1 || m->part < 0 || m->part >= m->n_parts) {
     set_global_error("tv_partition_layout: invalid arguments");
@@ -957,6 +1013,7 @@ int tv_destroy(void* ctx) {
   for (double* p : {c->cr[0], c->cr[1], c->cs[0], c->cs[1], c->cw1, c->wsend, c->dB, c->dtmp, c->Tfo})
     if (p) tv_dev_free(p);
   um_free(c->umd);
+  umdg_free(c->udgd);
   if (c->um_bmask) tv_dev_free(c->um_bmask);
   if (c->um_sidx) tv_dev_free(c->um_sidx);
   for (void* p : c->amg_bufs) tv_dev_free(p);
@@ -1035,6 +1092,11 @@ int tv_dof_coordinates(void* ctx, int space, double* xyz, size_t n_dofs) {
   const int fam = space == 0 ? c->fam_T : c->fam_S;
   const int64_t nown = space == 0 ? c->ownT_n : c->ownS_n;
   if ((int64_t)n_dofs != nown) return c->fail(TV_ERR_ARG, "n_dofs mismatch");
+  if (c->um && fam == TV_DG) {  // dof (cell, l), cell-major: the cell's l-th vertex
+    for (int64_t t = 0; t < nown; ++t)
+      std::memcpy(xyz + 3 * t, &c->um_xyz[3 * (size_t)c->um_cells[(size_t)t]], sizeof(double) * 3);
+    return TV_OK;
+  }
   if (c->um) {
     std::memcpy(xyz, c->um_xyz.data(), sizeof(double) * 3 * (size_t)nown);
     return TV_OK;
@@ -1157,10 +1219,14 @@ int tv_output_open_named(void* ctx, const char* dir, const int* field_ids, const
   // a partitioned unstructured mesh writes its own cells over all its local
   // vertices (the ghosts' values are kept current: visco runs on every local vertex)
   const size_t ncl = (size_t)c->um_own_cells << c->dim;
+  bool any_dg = false;  // a DG field among those asked for: the writer prepares the discontinuous mesh copy
+  for (int k = 0; k < n_fields; ++k)
+    if (field_ids[k] >= 0 && field_ids[k] < TV_NUM_FIELDS)
+      any_dg = any_dg || (c->f[field_ids[k]].space == 0 ? c->fam_T : c->fam_S) == TV_DG;
   Output* o = c->um ? output_create_unstructured(
                           dir, c->dim, c->um_xyz,
                           std::vector<int64_t>(c->um_cells.begin(), c->um_cells.begin() + std::min(ncl, c->um_cells.size())),
-                          err)
+                          any_dg, err)
                     : output_create(dir, c->dim, Xs, phys, err);
   if (!o) return c->fail(TV_ERR_STATE, "output: " + err);
   static const char* names[TV_NUM_FIELDS] = {

@@ -180,6 +180,11 @@ struct Ctx {
   std::vector<int64_t> um_cells;     // host copy: 2^dim per cell (input order)
   UmDevice* umd = nullptr;            // assembled operators, facet data (tv_um.hip)
   unsigned char* um_bmask = nullptr;  // boundary vertices (Dirichlet mode)
+  // DG1 temperature on an unstructured mesh (tv_umdg.hip): um is set as well, umg / umd / um_bmask are not
+  // (nothing that works on vertex dofs -- the SELL operator, the half stencils, AMG, the halo -- may run)
+  bool um_dg = false;
+  UmDgGrid udg{};
+  UmDgDevice* udgd = nullptr;
   // algebraic multigrid (options.preconditioner = TV_PC_AMG, unstructured, tv_amg.cpp)
   bool amg_on = false;
   std::vector<AmgLevel> amg;

@@ -338,6 +338,46 @@ void launch_um_diag(const UmGrid& g, const double* T, double* d, int invert, hip
 // logic.  Returns the number of partial records.
 int launch_um_japply_fused(const UmGrid& g, const double* T, const double* z, double* pA, double* pB, double* w,
                            const PcgState* st, double* partials, int it_host, const RedTail* tail, hipStream_t s);
+// its first launch alone: p <- z + (beta / betaold) p over n dofs (the CG and the DG general-mesh matvec)
+void launch_um_pvec(int64_t n, const PcgState* st, const double* z, double* pA, double* pB, int it_host,
+                    const RedTail& rt, hipStream_t s);
+
+// DG1 temperature on an unstructured mesh (SIPG, tv_umdg.hip).  Device dof of
+// (cell e, local vertex l): l nc + e, the box DG layout.  The T-independent
+// operator is assembled once into dense NL x NL blocks (NL = 2^dim), 1 + 2 dim
+// per cell: slot 0 the cell itself, slot 1 + lf the neighbour across local
+// facet lf = 2 axis + side.  Entry (i, j) of slot s of cell e sits at
+// ((s NL + i) NL + j) ncs + e (ncs = nc rounded up to 64: cell-fastest, so the
+// 64 cells of a wave at fixed i load a 512-byte run); no column indices: the
+// columns of slot s are the dofs j nc + nbr[(s - 1) ncs + e].
+struct UmDgGrid {
+  int dim;
+  int64_t nc, ncs;       // cells, block stride
+  const double* J;       // 1 + 2 dim slots: M + S in slot 0, S = dt alpha (K + SIPG) in the others   (J x)
+  const double* S0;      // slot 0 of S alone  (residual)
+  const double* M0;      // cell mass block    (residual: M (T - T_prev) formed before the product)
+  const int* nbr;        // [lf][cell] neighbour cell; across an exterior facet the cell itself, its block 0
+  const double* bvec;    // int phi_r
+  UmGrid rb;             // Robin terms (robin_row): fv, fw, boff, binc, brow over DG rows, and the constants
+};
+struct UmDgDevice;       // device allocations of one such mesh
+// The facets of a quadrilateral / hexahedral mesh as the SIPG form sees them
+// (tv_um_facets, include/tvfem.h): exterior {cell, lf}, interior {cell+, lf+,
+// cell-, lf-, orient}.  Host only.
+int um_facets(int dim, int64_t nv, int64_t nc, const int64_t* cells, std::vector<int64_t>& exterior2,
+              std::vector<int64_t>& interior5, std::string& err);
+// assembles the operator on the device (stream s, synchronised before return); g.rb holds the constants
+int umdg_setup(int dim, int64_t nv, const double* xyz, int64_t nc, const int64_t* cells, UmDgGrid& g,
+               UmDgDevice*& dev, hipStream_t s, std::string& err);
+void umdg_free(UmDgDevice* dev);
+int umdg_num_blocks(const UmDgGrid& g);  // partial records of the fused launch
+double umdg_matvec_bytes(const UmDgGrid& g);  // operator bytes one J x streams (blocks + neighbour table)
+void launch_umdg_residual(const UmDgGrid& g, const double* T, const double* Tp, double* F, hipStream_t s);
+void launch_umdg_japply(const UmDgGrid& g, const double* T, const double* x, double* y, hipStream_t s);
+void launch_umdg_diag(const UmDgGrid& g, const double* T, double* d, int invert, hipStream_t s);
+// as launch_um_japply_fused
+int launch_umdg_japply_fused(const UmDgGrid& g, const double* T, const double* z, double* pA, double* pB, double* w,
+                             const PcgState* st, double* partials, int it_host, const RedTail* tail, hipStream_t s);
 
 // ---- kernel launchers (tv_cg.hip, tv_dg.hip, tv_visco.hip, tv_pcg.hip) ----
 void launch_cg_residual(const CgGrid& g, const double* T, const double* Tp, double* F, hipStream_t s);
@@ -683,8 +723,9 @@ void launch_fill(double* x, int64_t n, double v, hipStream_t s);
 struct Output;
 Output* output_create(const std::string& dir, int dim, const std::vector<std::vector<double>>& Xs, const int* phys,
                       std::string& err);
+// with_dg: a DG field will be added, so the discontinuous copy of the mesh is prepared too
 Output* output_create_unstructured(const std::string& dir, int dim, const std::vector<double>& xyz,
-                                   const std::vector<int64_t>& cells, std::string& err);
+                                   const std::vector<int64_t>& cells, bool with_dg, std::string& err);
 bool output_add_field(Output* o, const std::string& name, int ncomp, bool dg, size_t n_values, std::string& err);
 bool output_start(Output* o, int device, std::string& err);
 double* output_acquire(Output* o, int* set);

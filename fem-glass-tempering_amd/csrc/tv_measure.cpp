@@ -42,8 +42,12 @@ int tv_kernel_bytes(void* ctx, int kernel, double* bytes) {
       // upper stencil slots of J(T) per row (112 B; the lower slots are the
       // neighbour rows' upper slots, counted once); else 8 B value + 4 B column
       // per stored SELL entry, padding included
-      *bytes = !c->um ? 16.0 * n
-                      : (c->umg.J14 ? (16.0 + 112.0) * n : 16.0 * n + 12.0 * (double)um_nnz(c->umd));
+      // DG on an unstructured mesh: the 1 + 2 d blocks of every cell (8 B per entry,
+      // no column indices) and the neighbour table
+      *bytes = !c->um      ? 16.0 * n
+               : c->um_dg  ? 16.0 * n + umdg_matvec_bytes(c->udg)
+               : c->umg.J14 ? (16.0 + 112.0) * n
+                            : 16.0 * n + 12.0 * (double)um_nnz(c->umd);
       break;
     case 1: {  // fused visco update, per dof
       int tf = 1;
@@ -119,9 +123,10 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
   // the J x of a solve: on a structured-topology unstructured mesh the Robin
   // terms at the current T are folded into the stencil once (as each Newton
   // iteration does), and the matvec alone is timed
-  if (c->um && (kernel == 0 || kernel == 10)) launch_um_robin_fold(c->umg, c->f[TV_F_T].ptr, c->stream);
+  if (c->um && !c->um_dg && (kernel == 0 || kernel == 10)) launch_um_robin_fold(c->umg, c->f[TV_F_T].ptr, c->stream);
   auto jx = [&]() {
-    if (c->um) launch_um_japply(c->umg, c->f[TV_F_T].ptr, c->pA, c->w, c->stream);
+    if (c->um_dg) launch_umdg_japply(c->udg, c->f[TV_F_T].ptr, c->pA, c->w, c->stream);
+    else if (c->um) launch_um_japply(c->umg, c->f[TV_F_T].ptr, c->pA, c->w, c->stream);
     else op_japply(c, c->f[TV_F_T].ptr, c->pA, c->w, nullptr, nullptr);
   };
   if (kernel == 11) {  // V-cycles on the current state (solver state reset: not converged)

@@ -359,7 +359,7 @@ Output* output_create(const std::string& dir, int dim, const std::vector<std::ve
 // unstructured mesh: vertices (3 per vertex) and cells (2^dim per cell, tensor
 // order) as given; cells written in VTK vertex order
 Output* output_create_unstructured(const std::string& dir, int dim, const std::vector<double>& xyz,
-                                   const std::vector<int64_t>& cells, std::string& err) {
+                                   const std::vector<int64_t>& cells, bool with_dg, std::string& err) {
   auto* o = new Output();
   o->series.dir = dir;
   o->series.dim = dim;
@@ -370,7 +370,18 @@ Output* output_create_unstructured(const std::string& dir, int dim, const std::v
     for (int q = 0; q < npc; ++q) vc[e * npc + q] = cells[e * npc + vtk[q]];
   o->series.n_nodes = (int64_t)xyz.size() / 3;
   o->series.n_cells = (int64_t)(cells.size() / npc);
-  o->series.n_dnodes = 0;
+  // the discontinuous copy for DG fields: node = (cell, l) in the reference's
+  // cell-major order, written when the first DG field opens (as the box writer);
+  // not built for a series of CG fields only (256 B per hexahedron on the host)
+  o->series.n_dnodes = with_dg ? (int64_t)cells.size() : 0;
+  o->series.dg_xyz.resize(with_dg ? 3 * cells.size() : 0);
+  o->series.dg_cells.resize(with_dg ? cells.size() : 0);
+  for (size_t e = 0; with_dg && e < cells.size() / npc; ++e)
+    for (int q = 0; q < npc; ++q) {
+      const size_t dn = e * npc + q;
+      for (int a = 0; a < 3; ++a) o->series.dg_xyz[3 * dn + a] = xyz[3 * (size_t)cells[dn] + a];
+      o->series.dg_cells[dn] = (int64_t)(e * npc + vtk[q]);
+    }
   if (!o->series.write_mesh("mesh", xyz, vc)) {
     err = o->series.err;
     delete o;

@@ -17,18 +17,21 @@ namespace tv {
 // operators
 // --------------------------------------------------------------------------------------
 void op_residual(Ctx* c, const double* T, const double* Tp, double* F) {
-  if (c->um) launch_um_residual(c->umg, T, Tp, F, c->stream);
+  if (c->um_dg) launch_umdg_residual(c->udg, T, Tp, F, c->stream);
+  else if (c->um) launch_um_residual(c->umg, T, Tp, F, c->stream);
   else if (c->fam_T == TV_CG) launch_cg_residual(c->cg, T, Tp, F, c->stream);
   else launch_dg_residual(c->dg, T, Tp, F, c->stream);
 }
 void op_diag(Ctx* c, const double* T, double* d, int invert) {
   // Jacobian "assembly": the diagonal for the Jacobi PC (J(T) itself is matrix-free)
-  if (c->um) launch_um_diag(c->umg, T, d, invert, c->stream);
+  if (c->um_dg) launch_umdg_diag(c->udg, T, d, invert, c->stream);
+  else if (c->um) launch_um_diag(c->umg, T, d, invert, c->stream);
   else if (c->fam_T == TV_CG) launch_cg_diag(c->cg, T, d, invert, c->stream);
   else launch_dg_diag(c->dg, T, d, invert, c->stream);
 }
 void op_japply(Ctx* c, const double* T, const double* x, double* y, double* partials, int* np) {
-  if (c->um) {  // (structured topology: the Robin terms at this T folded into the stencil first)
+  if (c->um_dg) launch_umdg_japply(c->udg, T, x, y, c->stream);
+  else if (c->um) {  // (structured topology: the Robin terms at this T folded into the stencil first)
     launch_um_robin_fold(c->umg, T, c->stream);
     launch_um_japply(c->umg, T, x, y, c->stream);
   }
@@ -36,6 +39,10 @@ void op_japply(Ctx* c, const double* T, const double* x, double* y, double* part
   else launch_dg_japply(c->dg, T, x, y, partials, np, c->stream);
 }
 bool op_japply_fused(Ctx* c, const double* T, int* np, const RedTail* tail, int it) {
+  if (c->um_dg) {
+    *np = launch_umdg_japply_fused(c->udg, T, c->z, c->pA, c->pB, c->w, c->st, c->partials, it, tail, c->stream);
+    return tail && tail->counter;
+  }
   if (c->um) {  // p <- z + b p, w <- J p, p.w and the reduction tail in one launch
     *np = launch_um_japply_fused(c->umg, T, c->z, c->pA, c->pB, c->w, c->st, c->partials, it, tail, c->stream);
     return tail && tail->counter;
@@ -481,7 +488,7 @@ int newton(Ctx* c, int* out_its, int* out_kits, int* out_conv, int step_end, boo
         c->dinv_interior = true;
       } else {
         op_diag(c, T, c->dinv, 1);
-        if (c->um) launch_um_robin_fold(c->umg, T, c->stream);  // J(u) of the solve (structured topology)
+        if (c->um && !c->um_dg) launch_um_robin_fold(c->umg, T, c->stream);  // J(u) of the solve (structured topology)
       }
     }
     dinv_fresh = false;

@@ -33,7 +33,7 @@ FIELD_ID = {n: i for i, n in enumerate(FIELDS)}
 
 # every C symbol include/tvfem.h declares (checked by tests/test_abi.py)
 EXPORTS = [
-    "tv_abi_version", "tv_last_error", "tv_default_options", "tv_default_params", "tv_create", "tv_create_unstructured", "tv_create_unstructured_part", "tv_partition_rcb", "tv_destroy",
+    "tv_abi_version", "tv_last_error", "tv_default_options", "tv_default_params", "tv_create", "tv_create_unstructured", "tv_create_unstructured_part", "tv_partition_rcb", "tv_um_facets", "tv_destroy",
     "tv_num_dofs", "tv_field_block_size", "tv_dof_coordinates", "tv_set_field", "tv_get_field",
     "tv_field_device_ptr", "tv_set_initial_condition", "tv_sync", "tv_residual", "tv_jacobian_apply",
     "tv_jacobian_diag", "tv_precond_apply", "tv_solve_T", "tv_visco_update", "tv_step", "tv_comm_unique_id_size",
@@ -145,6 +145,7 @@ def load_library():
                                                   C.POINTER(Params), C.POINTER(Options), C.c_int,
                                                   C.POINTER(C.c_void_p)]),
         "tv_partition_rcb": (C.c_int, [C.POINTER(UMeshDesc), C.c_int, C.POINTER(C.c_int)]),
+        "tv_um_facets": (C.c_int, [C.POINTER(UMeshDesc), i64p, i64p, i64p, i64p]),
         "tv_create": (C.c_int, [C.POINTER(MeshDesc), C.POINTER(FeConfig), C.POINTER(Params), C.POINTER(Options),
                                 C.c_int, C.POINTER(vp)]),
         "tv_destroy": (C.c_int, [vp]),

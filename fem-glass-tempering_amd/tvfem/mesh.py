@@ -7,7 +7,7 @@
   operators factorise on them (the fast path).
 * ``UnstructuredMesh``: vertices + quadrilateral / hexahedral cells of any
   shape (gmsh .msh files with 2D / 3D elements), assembled by the
-  element-local kernels (csrc/tv_um.hip).
+  element-local kernels (csrc/tv_um.hip; DG temperature: csrc/tv_umdg.hip).
 
 ``read_msh`` reads gmsh ASCII files (MSH 2.2 / 4.1): line meshes as a
 RectilinearMesh, quadrilateral / hexahedral meshes as an UnstructuredMesh.
@@ -80,6 +80,36 @@ class UnstructuredMesh:
 
     def __repr__(self):
         return f"UnstructuredMesh(dim={self.dim}, vertices={self.num_vertices}, cells={self.num_cells})"
+
+    def facets(self):
+        """``(exterior (n, 2), interior (n, 5))`` as the SIPG form of a DG
+        temperature sees them (tv_um_facets, host only): exterior rows ``(cell,
+        lf)``, interior rows ``(cell+, lf+, cell-, lf-, orient)`` with '+' the
+        lower cell index, ``lf = 2 axis + side``.  ``orient``: for '+' tangential
+        axis k (tangential axes in increasing order), bit 2k is the '-'
+        tangential axis it runs along and bit 2k + 1 is set where it runs
+        reversed.  Raises NativeError for a facet shared by more than two cells
+        or two cells that share a facet's vertices without sharing the facet."""
+        import ctypes as C
+
+        from . import _native as N
+        lib = N.load_library()
+        desc = N.UMeshDesc()
+        desc.dim = self.dim
+        xyz = np.ascontiguousarray(self.x)
+        cells = np.ascontiguousarray(self.cells, dtype=np.int64)
+        desc.n_vertices = xyz.shape[0]
+        desc.coords = xyz.ctypes.data_as(C.POINTER(C.c_double))
+        desc.n_cells = cells.shape[0]
+        desc.cells = cells.ctypes.data_as(C.POINTER(C.c_int64))
+        ni, ne = C.c_int64(), C.c_int64()
+        N.check(lib.tv_um_facets(C.byref(desc), C.byref(ni), None, C.byref(ne), None))
+        interior = np.zeros((ni.value, 5), dtype=np.int64)
+        exterior = np.zeros((ne.value, 2), dtype=np.int64)
+        i64p = C.POINTER(C.c_int64)
+        N.check(lib.tv_um_facets(C.byref(desc), None, interior.ctypes.data_as(i64p), None,
+                                 exterior.ctypes.data_as(i64p)))
+        return exterior, interior
 
     @classmethod
     def from_rectilinear(cls, mesh: "RectilinearMesh"):

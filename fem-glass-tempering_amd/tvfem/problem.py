@@ -196,11 +196,10 @@ class ThermoViscoProblem:
         um = isinstance(self.mesh, UnstructuredMesh)
         if um:
             # general quadrilateral / hexahedral cells: element-local kernels
-            # (csrc/tv_um.hip), CG1 spaces; partitioned: recursive coordinate
+            # (csrc/tv_um.hip, DG temperature csrc/tv_umdg.hip), CG1 / DG1 spaces;
+            # partitioned (CG1 only, the library refuses DG): recursive coordinate
             # bisection of the cells + a ghost layer (tvfem.parallel.ghosted_partition,
             # the mesh distribution of gmshio.read_from_msh at ThermoViscoProblem.py:27-28)
-            if self._fam["T"] != "CG" or self._fam["sigma"] != "CG":
-                raise NotImplementedError("unstructured meshes: CG temperature and stress spaces")
             local = self.mesh
             self._upart = None
             if n_parts > 1:

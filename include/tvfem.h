@@ -103,8 +103,9 @@ typedef struct {
  * shape, as gmsh writes them (geometry.py / gmshio.read_from_msh at
  * ThermoViscoProblem.py:27-28).  coords: 3 doubles per vertex; cells: 2^dim
  * vertex ids per cell in the tensor local order l = a + 2b + 4c (basix /
- * dolfinx order).  CG1 temperature and stress spaces; assembled by the
- * element-local kernels (csrc/tv_um.hip). */
+ * dolfinx order).  CG1 or DG1 temperature and stress spaces in every pairing;
+ * assembled by the element-local kernels (CG1 temperature: csrc/tv_um.hip,
+ * DG1 temperature: csrc/tv_umdg.hip). */
 typedef struct {
   int dim;
   int64_t n_vertices;
@@ -317,6 +318,13 @@ int tv_guard_check(int64_t* n_guarded, int64_t* n_damaged, int64_t* guard_bytes)
 
 int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params* params,
               const tv_options* opts, int device, void** ctx_out);
+/* A general quadrilateral / hexahedral mesh on one partition.  fe: CG1 or DG1
+ * for the temperature and for the stress, all four pairings (main.py runs DG1
+ * temperature with CG1 stress); DG dofs are numbered cell-major, dof = cell *
+ * 2^dim + local vertex, as on the box meshes.  Jacobi-PCG in the KSPCG form;
+ * TV_PC_AMG with a CG1 temperature only (TV_ERR_ARG with DG1 temperature).  The
+ * Dirichlet mode acts on a CG1 temperature; with DG1 it is accepted and has no
+ * effect, as on the box meshes. */
 int tv_create_unstructured(const tv_umesh_desc* mesh, const tv_fe_config* fe, const tv_params* params,
                            const tv_options* opts, int device, void** ctx_out);
 /* partition `part->part` of a distributed unstructured mesh (local mesh as
@@ -326,7 +334,8 @@ int tv_create_unstructured(const tv_umesh_desc* mesh, const tv_fe_config* fe, co
  * (TV_PC_AMG: at the first solve every rank gathers the GLOBAL T-independent
  * cell operator and builds the whole hierarchy -- host memory and setup time
  * per rank grow with the global nnz, O(27 x 12 B) per global vertex; refused
- * above 20M global rows, TV_ERR_ARG); Dirichlet mode as on one partition. */
+ * above 20M global rows, TV_ERR_ARG); Dirichlet mode as on one partition.
+ * CG1 spaces only: DG in either space is refused with TV_ERR_ARG. */
 int tv_create_unstructured_part(const tv_umesh_desc* local_mesh, const tv_upart_desc* part, const tv_fe_config* fe,
                                 const tv_params* params, const tv_options* opts, int device, void** ctx_out);
 int tv_destroy(void* ctx);
@@ -343,6 +352,19 @@ int tv_destroy(void* ctx);
  * Replaces the graph partitioner dolfinx applies when it distributes the mesh
  * read at ThermoViscoProblem.py:27-28. */
 int tv_partition_rcb(const tv_umesh_desc* mesh, int n_parts, int* part_out);
+/* Host only. The facets of a quadrilateral / hexahedral mesh as the SIPG form sees them
+ * (oracle facet_topology). Call with null arrays for the counts.
+ * lf = 2 * axis + side numbers a cell's local facets.  exterior2[2k..] = {cell,
+ * lf}, ascending in (cell, lf).  interior5[5k..] = {cell+, lf+, cell-, lf-,
+ * orient}, ascending in (cell+, lf+); '+' is the lower cell index.  orient says
+ * how the '-' facet's tangential reference coordinates follow the '+' facet's,
+ * the tangential axes of each facet taken in increasing order: for '+'
+ * tangential axis k, bit 2k holds the '-' tangential axis it runs along and bit
+ * 2k + 1 is 1 when it runs reversed (xi- = 1 - xi+).  TV_ERR_ARG for a facet
+ * shared by more than two cells or a shared vertex set that is not a facet of
+ * both cells. */
+int tv_um_facets(const tv_umesh_desc* mesh, int64_t* n_interior, int64_t* interior5,
+                 int64_t* n_exterior, int64_t* exterior2);
 int tv_partition_layout(const tv_mesh_desc* mesh, int64_t* out13);
 
 /* sizes: owned dofs of the T space / sigma space on this partition; block
