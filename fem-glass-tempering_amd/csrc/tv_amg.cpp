@@ -40,6 +40,9 @@
 //     (544K vertices, the Newton right-hand side): Jacobi-PCG 35 iterations,
 //     this cycle 12, a multiplicative V(1,1) 11 (at three fine J x per
 //     iteration instead of one), unsmoothed aggregation 16.
+//   * DG1 temperature (options.preconditioner = TV_PC_AUX, aux_setup below):
+//     the same hierarchy under the CG1 space of the mesh, which serves the DG
+//     level as auxiliary space (level-0 kernels: tv_umdg_aux.hip).
 #include <numeric>
 #include <thread>
 
@@ -393,8 +396,8 @@ int upload_mat(Ctx* c, const Csr& M, Sell& out, bool csr, bool fp32, int64_t sor
 }
 
 // the fine SELL-64 operator back on the host as CSR (padding entries dropped)
-int fine_csr(Ctx* c, Csr& A) {
-  const Sell S = um_operator(c->umg);
+int fine_csr(Ctx* c, const UmGrid& g, Csr& A) {
+  const Sell S = um_operator(g);
   std::vector<int64_t> soff((size_t)S.nslice + 1);
   HIPC(hipMemcpy(soff.data(), S.soff, sizeof(int64_t) * soff.size(), hipMemcpyDeviceToHost));
   const int64_t nnz = soff[S.nslice];
@@ -620,13 +623,169 @@ static int amg_build(Ctx* c, Csr A, int64_t row0, int64_t nrow, const int64_t* g
 int amg_setup(Ctx* c) {
   if (!c->um || c->n_parts > 1) return c->fail(TV_ERR_ARG, "AMG: unstructured meshes on one partition");
   Csr A;
-  if (int e = fine_csr(c, A)) return e;
+  if (int e = fine_csr(c, c->umg, A)) return e;
   const int64_t n = A.n;
   if (c->umg.J14 != nullptr) {  // structured topology (tv_um.hip): geometric transfers
     const int64_t grid[3] = {c->umg.s1, c->umg.s2 / c->umg.s1, c->umg.nv / c->umg.s2};
     return amg_build(c, std::move(A), 0, n, grid);
   }
   return amg_build(c, std::move(A), 0, n);
+}
+
+// Auxiliary-space multigrid for DG1 temperature on an unstructured mesh
+// (options.preconditioner = TV_PC_AUX, one partition).  Level 0 is the DG space
+// with the cell-block Jacobi smoother of tv_umdg_aux.hip; level 1 (c->amg[0])
+// is the CG1 space of the same mesh, its operator the CG1 cell operator
+// V = M + dt alpha K assembled from the CG path's element rows -- the Galerkin
+// operator P^T V_dg P of the injection P: continuous functions have no jumps,
+// so the SIPG terms vanish -- with dinv = 1 / diag V (Robin stays on the fine
+// level, as in amg_setup) and omega = 2 / (1.1 lambda_max); below it amg_build
+// continues from A = V exactly as for a CG mesh (aggregation).  The level
+// 0 <-> 1 transfers are index tables, no stored values: vertex -> DG copies
+// (int32, slot-major, padded with -1 to the largest valence, copies ascending,
+// vertex stride a multiple of 64: an atomic-free sum in a fixed order) and
+// (cell, l) -> vertex.  options.mg_levels counts the DG and the CG level.
+int aux_setup(Ctx* c) {
+  if (!c->um_dg || c->n_parts > 1)
+    return c->fail(TV_ERR_ARG, "TV_PC_AUX: DG temperature on an unstructured mesh, one partition");
+  if (c->O.mg_levels == 1)
+    return c->fail(TV_ERR_ARG, "TV_PC_AUX: mg_levels counts the DG and the CG level: 0 (automatic) or >= 2");
+  const int dim = c->dim, nl = 1 << dim, nlf = 2 * dim;
+  const UmDgGrid& g = c->udg;
+  const int64_t nc = g.nc, ncs = g.ncs, nv = (int64_t)c->um_xyz.size() / 3;
+  const int64_t* cells = c->um_cells.data();
+  UmDgAux& a = c->aux;
+  // -- vertex -> DG copies: device dof l nc + e, ascending
+  std::vector<int> val_of((size_t)nv, 0);
+  for (int64_t k = 0; k < nc * nl; ++k) val_of[(size_t)cells[k]]++;
+  int nval = 0;
+  for (int64_t v = 0; v < nv; ++v) {
+    if (val_of[(size_t)v] == 0) return c->fail(TV_ERR_ARG, "TV_PC_AUX: a vertex that belongs to no cell");
+    nval = std::max(nval, val_of[(size_t)v]);
+  }
+  const int64_t vs = (nv + 63) / 64 * 64;
+  std::vector<int> vinc((size_t)nval * vs, -1), cellv((size_t)nl * ncs, 0), fillv((size_t)nv, 0);
+  for (int l = 0; l < nl; ++l)
+    for (int64_t e = 0; e < nc; ++e) {
+      const int64_t v = cells[e * nl + l];
+      vinc[(size_t)((int64_t)fillv[(size_t)v]++ * vs + v)] = (int)((int64_t)l * nc + e);
+      cellv[(size_t)((int64_t)l * ncs + e)] = (int)v;
+    }
+  // -- exterior facets per cell, in the order of UmDgGrid::rb.fw (um_facets' exterior list)
+  std::vector<int64_t> ext, in;
+  std::string err;
+  if (um_facets(dim, nv, nc, cells, ext, in, err)) return c->fail(TV_ERR_ARG, err);
+  std::vector<int> cfac((size_t)nlf * ncs, -1), bcell;
+  for (int64_t f = 0; f < (int64_t)ext.size() / 2; ++f) {
+    const int64_t e = ext[2 * f], lf = ext[2 * f + 1];
+    cfac[(size_t)(lf * ncs + e)] = (int)f;
+    if (bcell.empty() || bcell.back() != (int)e) bcell.push_back((int)e);  // the list is sorted by cell
+  }
+  a.nv = nv;
+  a.vs = vs;
+  a.nval = nval;
+  a.nbc = (int64_t)bcell.size();
+  int *vinc_d, *cellv_d, *cfac_d, *bcell_d;
+  if (int e = amg_upload(c, vinc, &vinc_d)) return e;
+  if (int e = amg_upload(c, cellv, &cellv_d)) return e;
+  if (int e = amg_upload(c, cfac, &cfac_d)) return e;
+  if (int e = amg_upload(c, bcell, &bcell_d)) return e;
+  a.vinc = vinc_d;
+  a.cellv = cellv_d;
+  a.cfac = cfac_d;
+  a.bcell = bcell_d;
+  if (int e = amg_alloc(c, (size_t)(nl * (nl + 1) / 2) * (size_t)ncs, &a.binv)) return e;
+  if (int e = amg_alloc(c, 1, &a.flag)) return e;
+  HIPC(hipMemsetAsync(a.binv, 0, sizeof(double) * (size_t)(nl * (nl + 1) / 2) * (size_t)ncs, c->stream));
+  HIPC(hipMemsetAsync(a.flag, 0, sizeof(int), c->stream));
+  // -- the block inverses of every cell at the T = 0 of a fresh context; the
+  // cells with an exterior facet follow T from the first solve on (aux_refresh)
+  launch_umdg_binv(g, a, c->f[TV_F_T].ptr, 1, c->stream);
+  HIPC(hipGetLastError());
+  int bad = 0;
+  HIPC(hipMemcpyAsync(&bad, a.flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPC(hipStreamSynchronize(c->stream));
+  if (bad) return c->fail(TV_ERR_ARG, "TV_PC_AUX: cell block not positive definite");
+  // -- level 1: V of the CG1 space over the pattern "vertices of the cells around a vertex"
+  Csr A;
+  A.n = A.m = nv;
+  A.ptr.assign((size_t)nv + 1, 0);
+  {
+    std::vector<int> buf;
+    for (int64_t v = 0; v < nv; ++v) {
+      buf.clear();
+      for (int k = 0; k < val_of[(size_t)v]; ++k) {
+        const int64_t e = vinc[(size_t)((int64_t)k * vs + v)] % nc;
+        for (int j = 0; j < nl; ++j) buf.push_back((int)cells[e * nl + j]);
+      }
+      std::sort(buf.begin(), buf.end());
+      buf.erase(std::unique(buf.begin(), buf.end()), buf.end());
+      A.col.insert(A.col.end(), buf.begin(), buf.end());
+      A.ptr[(size_t)v + 1] = (int64_t)A.col.size();
+    }
+  }
+  A.val.assign(A.col.size(), 0.0);
+  {
+    // setup-only device arrays, released below
+    const size_t nb0 = c->amg_bufs.size();
+    std::vector<double> Xh((size_t)nv);
+    double* Xd[3];
+    for (int s = 0; s < 3; ++s) {
+      for (int64_t v = 0; v < nv; ++v) Xh[(size_t)v] = c->um_xyz[(size_t)(3 * v + s)];
+      if (int e = amg_upload(c, Xh, &Xd[s])) return e;
+    }
+    int64_t* ptr_d;
+    int* col_d;
+    double* val_d;
+    if (int e = amg_upload(c, A.ptr, &ptr_d)) return e;
+    if (int e = amg_upload(c, A.col, &col_d)) return e;
+    if (int e = amg_upload(c, A.val, &val_d)) return e;
+    launch_aux_assemble_v(dim, a, nc, ncs, Xd[0], Xd[1], Xd[2], ptr_d, col_d, g.rb.dt_alpha, val_d, c->stream);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(A.val.data(), val_d, sizeof(double) * A.val.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPC(hipStreamSynchronize(c->stream));
+    while (c->amg_bufs.size() > nb0) {
+      HIPC(tv_dev_free(c->amg_bufs.back()));
+      c->amg_bufs.pop_back();
+    }
+  }
+  {  // exact zeros dropped, as fine_csr does for the CG path's operator (the aggregation's pattern)
+    Csr B;
+    B.n = B.m = nv;
+    B.ptr.assign((size_t)nv + 1, 0);
+    for (int64_t r = 0; r < nv; ++r) {
+      for (int64_t k = A.ptr[r]; k < A.ptr[r + 1]; ++k)
+        if (A.val[k] != 0.0) {
+          B.col.push_back(A.col[k]);
+          B.val.push_back(A.val[k]);
+        }
+      B.ptr[(size_t)r + 1] = (int64_t)B.col.size();
+    }
+    A = std::move(B);
+  }
+  {
+    c->amg.emplace_back();
+    AmgLevel& L = c->amg.back();
+    L.n = nv;
+    if (int e = upload_mat(c, A, L.A, false, false, 0, &L.a_nnz)) return e;
+    const std::vector<double> dc = diag_inv(A);
+    for (double v : dc)
+      if (!(v > 0.0) || !std::isfinite(v)) return c->fail(TV_ERR_ARG, "TV_PC_AUX: CG1 operator not positive definite");
+    L.omega = 2.0 / (1.1 * lam_max(A, dc, 20));
+    if (int e = amg_upload(c, dc, &L.dinv)) return e;
+    for (double** v : {&L.b, &L.x, &L.w})
+      if (int e = amg_alloc(c, (size_t)nv, v)) return e;
+  }
+  c->aux_on = true;
+  return amg_build(c, std::move(A), 0, nv);
+}
+
+void aux_refresh(Ctx* c, const double* T) { launch_umdg_binv(c->udg, c->aux, T, 0, c->stream); }
+
+void aux_smooth(Ctx* c, const PcgState* st, const double* b, double omega, double* x) {
+  // the update kernel's init form reads b through its r argument and writes x only
+  launch_umdg_aux_update(c->udg, c->aux, st, nullptr, nullptr, nullptr, omega, const_cast<double*>(b), nullptr, x, 0, 1,
+                         c->stream);
 }
 
 // The hierarchy of a partition of a distributed unstructured mesh (collective,
@@ -641,7 +800,7 @@ int amg_setup(Ctx* c) {
 int amg_setup_part(Ctx* c) {
   if (!c->um || c->n_parts < 2) return c->fail(TV_ERR_ARG, "AMG: partitioned unstructured meshes");
   Csr Al;
-  if (int e = fine_csr(c, Al)) return e;  // owned rows, local columns
+  if (int e = fine_csr(c, c->umg, Al)) return e;  // owned rows, local columns
   const int64_t nown = c->ownT_n, nloc = c->nT, off = c->globT_off;
   hipStream_t s = c->stream;
   double* dv = nullptr;
@@ -742,6 +901,11 @@ static const double* amg_level(Ctx* c, size_t l) {
 // with the (z.z, z.r) records and the KSPCG tail
 int amg_apply0(Ctx* c, const RedTail* tail) {
   AmgLevel& L1 = c->amg[0];
+  if (c->aux_on) {  // DG level 0 over the CG1 level: vertex sums down, injection up (tv_umdg_aux.hip)
+    launch_umdg_aux_restrict(c->aux, c->st, c->r, L1.dinv, L1.omega, L1.b, L1.x, c->stream);
+    const double* x1 = amg_level(c, 1);
+    return launch_umdg_aux_prolong0(c->udg, c->aux, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
+  }
   if (c->n_parts > 1) {  // the partial restriction of the owned fine rows, summed over the ranks
     launch_amg_restrict(L1.R, c->st, c->r, nullptr, nullptr, 0.0, L1.b, nullptr, c->stream);
     if (int e = allreduce_vec(c, L1.b, L1.n)) return -e;
@@ -769,6 +933,13 @@ double amg_cycle_bytes(const Ctx* c) {
   const double t0 = L1.geo0 ? 0.0 : 8.0;
   double b = t0 * (double)L1.r_nnz + 8.0 * n0 + 24.0 * (double)L1.n;
   b += t0 * (double)L1.p_nnz + 8.0 * (double)L1.n + 24.0 * n0;
+  if (c->aux_on) {
+    // the auxiliary-space cycle as tv_time_kernel runs it (with its pre-smoothing x0 = omega0 B^-1 r): the
+    // packed block inverses, r in and x0 out, and the two transfers' index tables (no stored values)
+    const double nl = (double)(1 << c->dim);
+    b += 8.0 * (nl * (nl + 1.0) / 2.0) * (double)c->udg.nc + 16.0 * n0;
+    b += 4.0 * (double)c->aux.nval * (double)c->aux.vs + 4.0 * n0;
+  }
   for (size_t l = 0; l + 1 < c->amg.size(); ++l) {
     const AmgLevel& L = c->amg[l];
     const AmgLevel& C = c->amg[l + 1];

@@ -741,6 +741,10 @@ int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params*
     set_global_error("TV_PC_AMG: unstructured meshes (the box meshes take TV_PC_GMG)");
     return TV_ERR_ARG;
   }
+  if (c->O.preconditioner == TV_PC_AUX) {
+    set_global_error("TV_PC_AUX: DG temperature on unstructured meshes (the box meshes take TV_PC_GMG)");
+    return TV_ERR_ARG;
+  }
   int rc = setup_mesh(c.get(), mesh);
   if (rc == TV_OK) rc = setup_fields(c.get());
   if (rc == TV_OK && c->O.preconditioner == TV_PC_GMG) rc = mg_setup(c.get());
@@ -768,7 +772,11 @@ static int setup_umesh(Ctx* c, const tv_umesh_desc* m, const tv_upart_desc* pd) 
                                "are not implemented)");
   if (c->fam_T == TV_DG && c->O.preconditioner == TV_PC_AMG)
     return c->fail(TV_ERR_ARG, "unstructured meshes: TV_PC_AMG needs a CG temperature space (the aggregation works "
-                               "on the vertex operator; DG temperature takes TV_PC_JACOBI)");
+                               "on the vertex operator; DG temperature takes TV_PC_JACOBI or the auxiliary-space "
+                               "multigrid TV_PC_AUX)");
+  if (c->fam_T != TV_DG && c->O.preconditioner == TV_PC_AUX)
+    return c->fail(TV_ERR_ARG, "unstructured meshes: TV_PC_AUX needs a DG temperature space (its level 0 is the "
+                               "cell-block smoother of the DG operator; CG temperature takes TV_PC_AMG)");
   if (m->n_vertices < 1 || m->n_cells < 1 || !m->coords || !m->cells) return c->fail(TV_ERR_ARG, "empty mesh");
   if (m->n_vertices >= INT32_MAX) return c->fail(TV_ERR_ARG, "unstructured meshes: < 2^31 vertices");
   const int nl = 1 << d;
@@ -904,9 +912,9 @@ static int create_unstructured(const tv_umesh_desc* mesh, const tv_upart_desc* p
     set_global_error("HIP stream/event creation failed");
     return TV_ERR_HIP;
   }
-  if (c->O.preconditioner != TV_PC_JACOBI && c->O.preconditioner != TV_PC_AMG) {
-    set_global_error("unstructured meshes: preconditioner TV_PC_JACOBI or TV_PC_AMG (the box multigrid needs a "
-                     "rectilinear mesh)");
+  if (c->O.preconditioner != TV_PC_JACOBI && c->O.preconditioner != TV_PC_AMG && c->O.preconditioner != TV_PC_AUX) {
+    set_global_error("unstructured meshes: preconditioner TV_PC_JACOBI, TV_PC_AMG or TV_PC_AUX (the box multigrid "
+                     "needs a rectilinear mesh)");
     return TV_ERR_ARG;
   }
   int rc = setup_umesh(c.get(), mesh, part);
@@ -914,6 +922,7 @@ static int create_unstructured(const tv_umesh_desc* mesh, const tv_upart_desc* p
   // a partition builds its (agglomerated) hierarchy at its first solve: the
   // setup gathers the global operator through the communicator set after creation
   if (rc == TV_OK && c->O.preconditioner == TV_PC_AMG && c->n_parts < 2) rc = amg_setup(c.get());
+  if (rc == TV_OK && c->O.preconditioner == TV_PC_AUX) rc = aux_setup(c.get());
   if (rc == TV_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = c->fail(TV_ERR_HIP, "sync failed");
   if (rc != TV_OK) {
     set_global_error(c->err);
@@ -1324,7 +1333,8 @@ int tv_set_dirichlet(void* ctx, int enable, double value) {
     return c->fail(TV_ERR_STATE, "Dirichlet condition: only with model_mode = TV_MODEL_PAPER (the reference's "
                                  "own path cannot run, ThermoViscoProblem.py:236-243)");
   if (enable && c->amg_on)
-    return c->fail(TV_ERR_STATE, "Dirichlet condition: not with TV_PC_AMG (Jacobi or the box multigrid)");
+    return c->fail(TV_ERR_STATE, c->aux_on ? "Dirichlet condition: not with TV_PC_AUX (Jacobi or the box multigrid)"
+                                           : "Dirichlet condition: not with TV_PC_AMG (Jacobi or the box multigrid)");
   hipSetDevice(c->device);
   c->dir_on = enable != 0;
   c->dir_value = value;

@@ -189,6 +189,10 @@ struct Ctx {
   bool amg_on = false;
   std::vector<AmgLevel> amg;
   std::vector<void*> amg_bufs;
+  // auxiliary-space multigrid (TV_PC_AUX: um_dg, tv_amg.cpp aux_setup): amg[0] is the CG1 space of the
+  // mesh (A = its cell operator V, no stored transfers), amg[1..] the aggregation hierarchy below it
+  bool aux_on = false;
+  UmDgAux aux{};
   // partitioned unstructured mesh (tv_create_unstructured_part): owned vertices
   // first, ghosts grouped by owner; per neighbour k: the ghosts received from
   // um_peer[k] at [nown + um_roff[k], + um_rcnt[k]), the owned values sent to it
@@ -296,6 +300,11 @@ constexpr int kTsCap = 1 << 15;                // timestamp slots of the in-solv
 // ---- tv_amg.cpp ----
 int amg_setup(Ctx* c);
 int amg_setup_part(Ctx* c);  // collective (partitioned unstructured mesh), at the first solve
+int aux_setup(Ctx* c);       // TV_PC_AUX: the DG level's tables and block inverses, the CG1 level, the hierarchy
+// the cell blocks of J(T) that follow T (exterior facets), inverted again: per Newton iteration
+void aux_refresh(Ctx* c, const double* T);
+// x = omega B^-1 b over the DG dofs (x may be b)
+void aux_smooth(Ctx* c, const PcgState* st, const double* b, double omega, double* x);
 int amg_apply0(Ctx* c, const RedTail* tail);
 double amg_cycle_bytes(const Ctx* c);
 

@@ -379,6 +379,39 @@ void launch_umdg_diag(const UmDgGrid& g, const double* T, double* d, int invert,
 int launch_umdg_japply_fused(const UmDgGrid& g, const double* T, const double* z, double* pA, double* pB, double* w,
                              const PcgState* st, double* partials, int it_host, const RedTail* tail, hipStream_t s);
 
+// Level 0 of the auxiliary-space multigrid on such a mesh (TV_PC_AUX, tv_umdg_aux.hip; the tables are built by
+// tv_amg.cpp aux_setup): the packed inverses of the cells' diagonal blocks and the index tables of the
+// DG <-> CG1 transfers (P copies a vertex value into its DG copies, P^T sums them).
+struct UmDgAux {
+  int64_t nv, vs;        // vertices of the mesh, incidence stride (nv rounded up to 64)
+  int nval;              // the largest number of cells around a vertex
+  const int* vinc;       // [k][vertex] DG dof of the vertex's k-th copy (ascending), -1 beyond its valence
+  const int* cellv;      // [l][cell] vertex of DG dof (cell, l), stride ncs
+  const int* cfac;       // [lf][cell] exterior facet (index into rb.fw) or -1, stride ncs
+  const int* bcell;      // the nbc cells with an exterior facet (their blocks follow T)
+  int64_t nbc;
+  double* binv;          // B_e^-1, packed lower triangle: entry i (i + 1) / 2 + j of cell e at (..) ncs + e
+  int* flag;             // raised by a non-positive Cholesky pivot at creation
+};
+// val (CSR over the pattern ptr / col, columns sorted, zeroed) += the CG1 cell operator M + dt alpha K of the mesh
+void launch_aux_assemble_v(int dim, const UmDgAux& a, int64_t nc, int64_t ncs, const double* X0, const double* X1,
+                           const double* X2, const int64_t* ptr, const int* col, double dt_alpha, double* val,
+                           hipStream_t s);
+// B^-1 of every cell (all = 1, with the pivot check) or of the cells of a.bcell at temperature T
+void launch_umdg_binv(const UmDgGrid& g, const UmDgAux& a, const double* T, int all, hipStream_t s);
+// r <- r - a w, x0 <- omega B^-1 r, dx moved every second iteration (launch_dg_bupdate's contract);
+// init: x0 <- omega B^-1 r only (st may be null, x0 may be r)
+void launch_umdg_aux_update(const UmDgGrid& g, const UmDgAux& a, const PcgState* st, const double* pA,
+                            const double* pB, const double* w, double omega, double* r, double* dx, double* x0,
+                            int it_host, int init, hipStream_t s);
+// b_1 = P^T r (vertex sums), x_1 = omega_1 dinv_1 b_1
+void launch_umdg_aux_restrict(const UmDgAux& a, const PcgState* st, const double* r, const double* dinv1,
+                              double omega1, double* b1, double* x1, hipStream_t s);
+// z = x0 + P x_1, (z.z, z.r) records and the reduction tail; returns the record count
+int launch_umdg_aux_prolong0(const UmDgGrid& g, const UmDgAux& a, const PcgState* st, const double* x1,
+                             const double* x0, const double* r, double* z, double* partials, const RedTail* tail,
+                             hipStream_t s);
+
 // ---- kernel launchers (tv_cg.hip, tv_dg.hip, tv_visco.hip, tv_pcg.hip) ----
 void launch_cg_residual(const CgGrid& g, const double* T, const double* Tp, double* F, hipStream_t s);
 // the residual plus the boundary rows of dinv = 1 / diag J(T) in its boundary

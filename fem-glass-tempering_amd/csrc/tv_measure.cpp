@@ -101,6 +101,12 @@ int tv_kernel_bytes(void* ctx, int kernel, double* bytes) {
       *bytes = b;
       break;
     }
+    case 18: {  // TV_PC_AUX: the per-Newton block refresh -- the lower triangle of slot 0 in, the packed inverse out
+      if (!c->aux_on) return c->fail(TV_ERR_ARG, "kernel 18: preconditioner TV_PC_AUX not enabled");
+      const double nl = (double)(1 << c->dim);
+      *bytes = (16.0 * (nl * (nl + 1.0) / 2.0) + 8.0 * nl + 4.0 * (2.0 * c->dim + 1.0)) * (double)c->aux.nbc;
+      break;
+    }
     default:
       return c->fail(TV_ERR_ARG, "unknown kernel id");
   }
@@ -140,15 +146,20 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
       if (int e = mg_prepare(c, c->f[TV_F_T].ptr)) return e;
     }
     if (int e = mg_dg_weight(c, c->f[TV_F_T].ptr)) return e;
+    if (c->aux_on) aux_refresh(c, c->f[TV_F_T].ptr);  // the cell blocks at the current T, as a Newton iteration sets them
   }
+  if (kernel == 18 && !c->aux_on) return c->fail(TV_ERR_ARG, "kernel 18: preconditioner TV_PC_AUX not enabled");
   auto one = [&]() -> int {
     int np = 0;
     switch (kernel) {
       case 11:  // partitioned: the distributed V-cycle, its exchanges included (every rank calls this)
         if (c->n_parts > 1) return mg_apply0_dist(c, c->f[TV_F_T].ptr, nullptr);
+        // the auxiliary-space cycle with its pre-smoothing x0 = omega0 B^-1 r (in a solve: the update launch)
+        if (c->aux_on) aux_smooth(c, c->st, c->r, c->mg_omega0, c->mgx);
         np = mg_apply0(c, c->f[TV_F_T].ptr, nullptr);
         return np < 0 ? -np : TV_OK;
       case 0: jx(); return TV_OK;
+      case 18: aux_refresh(c, c->f[TV_F_T].ptr); return TV_OK;
       case 1: return visco(c, false);
       case 2: op_residual(c, c->f[TV_F_T].ptr, c->f[TV_F_T_PREV].ptr, c->r); return TV_OK;
       case 3:

@@ -95,13 +95,15 @@ int mg_dg_lambda(Ctx* c, const double* T, double* lam) {
   else if (!c->um) launch_dg_diag(c->dg, T, c->dinv, 1, c->stream);
   std::vector<double> prt(1024);
   double l = 0.0;
-  if (c->um) op_diag(c, T, c->dinv, 1);  // the algebraic multigrid's level 0: point Jacobi of J(T)
+  if (c->aux_on) aux_refresh(c, T);  // the auxiliary-space level 0: the cell blocks of J(T)
+  else if (c->um) op_diag(c, T, c->dinv, 1);  // the algebraic multigrid's level 0: point Jacobi of J(T)
   for (int it = 0; it < 30; ++it) {
     if (part)
       if (int e = halo(c, c->mgx)) return e;
     op_japply(c, T, c->mgx, c->w, nullptr, nullptr);
     if (c->dggface) launch_dg_bsmooth(c->dg, nullptr, c->w, nullptr, c->dggface, 1.0, c->w, 0, c->stream);  // in place, per cell
-    const int nb = launch_mg_pow(n, c->dggface ? nullptr : c->dinv, c->w, c->partials, c->stream);
+    if (c->aux_on) aux_smooth(c, nullptr, c->w, 1.0, c->w);  // B^-1 where dinv is applied (in place, per cell)
+    const int nb = launch_mg_pow(n, (c->dggface || c->aux_on) ? nullptr : c->dinv, c->w, c->partials, c->stream);
     HIPC(hipMemcpyAsync(prt.data(), c->partials, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     double s2 = 0.0;
@@ -576,6 +578,9 @@ int mg_iteration(Ctx* c, const double* T, int it) {
   if (c->dggface)
     launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it, 0,
                       c->stream);
+  else if (c->aux_on)
+    launch_umdg_aux_update(c->udg, c->aux, c->st, c->pA, c->pB, c->w, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it,
+                           0, c->stream);
   else
     launch_mg_update(n, c->st, c->pA, c->pB, c->w, &fa, c->dinv, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it, 0,
                      c->stream);
@@ -613,6 +618,9 @@ int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
   if (c->dggface)
     launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0, 1,
                       c->stream);  // dx <- 0, x0 <- omega B^-1 r
+  else if (c->aux_on)
+    launch_umdg_aux_update(c->udg, c->aux, c->st, c->pA, c->pB, c->w, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0,
+                           1, c->stream);  // x0 <- omega B^-1 r (cell blocks)
   else
     launch_mg_update(n, c->st, c->pA, c->pB, c->w, nullptr, c->dinv, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0, 1,
                      c->stream);  // dx <- 0, x0 <- omega dinv r
@@ -685,7 +693,9 @@ int tv_precond_apply(void* ctx, const double* r_dev, double* z_dev) {
   const int64_t n = c->nT;
   hipStream_t s = c->stream;
   // the PC setup of the Newton iteration at this T
-  if (!c->dggface) {
+  if (c->aux_on) {
+    aux_refresh(c, T);  // the cell blocks that follow T
+  } else if (!c->dggface) {
     if (!c->um && c->fam_T == TV_CG) {
       launch_cg_diag(c->cg, T, c->dinv, 1, s, c->dinv_interior);
       c->dinv_interior = true;
@@ -708,6 +718,8 @@ int tv_precond_apply(void* ctx, const double* r_dev, double* z_dev) {
     HIPC(hipMemcpyAsync(c->r, r_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
     if (c->dggface)  // x0 = omega0 B^-1 r (cell blocks)
       launch_dg_bsmooth(c->dg, c->st, c->r, nullptr, c->dggface, c->mg_omega0, c->mgx, 0, s);
+    else if (c->aux_on)
+      aux_smooth(c, c->st, c->r, c->mg_omega0, c->mgx);
     else
       launch_mg_jacobi(n, c->st, c->r, nullptr, nullptr, c->dinv, c->mg_omega0, c->mgx, 0, s);
     if (const int nrec = mg_apply0(c, T, nullptr); nrec < 0) return -nrec;

@@ -17,7 +17,7 @@ TV_CG, TV_DG = 0, 1
 TV_PCG_AUTO, TV_PCG_KSPCG, TV_PCG_SINGLE_REDUCTION = 0, 1, 2
 TV_MODEL_REFERENCE, TV_MODEL_PAPER, TV_MODEL_PAPER_EXACT = 0, 1, 2  # PAPER_EXACT: ensembles only
 TV_RELAX_TAYLOR, TV_RELAX_EXACT = 0, 1  # tv_set_relaxation (single-problem contexts)
-TV_PC_JACOBI, TV_PC_GMG, TV_PC_AMG = 0, 1, 2
+TV_PC_JACOBI, TV_PC_GMG, TV_PC_AMG, TV_PC_AUX = 0, 1, 2, 3
 TV_DG_KERNEL_AUTO, TV_DG_KERNEL_TILE, TV_DG_KERNEL_CELLS = 0, 1, 2
 TV_MG_COUPLING_AUTO, TV_MG_COUPLING_GLOBAL, TV_MG_COUPLING_LOCAL = 0, 1, 2
 ABI_VERSION = 8

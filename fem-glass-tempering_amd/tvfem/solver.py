@@ -67,8 +67,9 @@ class _PC:
 
     def getType(self) -> str:
         # the reference asks for "gamg" (ThermoViscoProblem.py:344); the context
-        # runs point Jacobi, the box multigrid or the algebraic multigrid
-        return {"jacobi": "jacobi", "gmg": "mg", "amg": "gamg"}[self._p.preconditioner]
+        # runs point Jacobi, the box multigrid, the algebraic multigrid or, for a DG
+        # temperature on a general mesh, the auxiliary-space one (both in GAMG's role)
+        return {"jacobi": "jacobi", "gmg": "mg", "amg": "gamg", "aux": "gamg"}[self._p.preconditioner]
 
 
 class NewtonSolver:

@@ -175,8 +175,12 @@ typedef struct {
                              TV_MODEL_PAPER_EXACT (ensembles only; a single
                              problem: tv_set_relaxation)                        */
   int preconditioner;     /* TV_PC_JACOBI (default) / TV_PC_GMG (box meshes) /
-                             TV_PC_AMG (unstructured meshes, one partition)      */
-  int mg_levels;          /* GMG: levels incl. the fine one (0: automatic)       */
+                             TV_PC_AMG (unstructured meshes, CG1 temperature) /
+                             TV_PC_AUX (unstructured meshes, DG1 temperature,
+                             one partition)                                      */
+  int mg_levels;          /* GMG: levels incl. the fine one (0: automatic);
+                             TV_PC_AUX: the DG and the CG1 level count (0, or
+                             >= 2; 2: DG + CG1 only)                             */
   int dg_kernel;          /* 3D DG1 Jacobian: TV_DG_KERNEL_AUTO / _TILE / _CELLS */
   int dg_tile_chunk;      /* planes per marching DG tile (0: automatic = 5)      */
   int mg_replicate_nodes; /* partitioned GMG: coarse levels of at most this many
@@ -231,6 +235,13 @@ typedef struct {
                          smoothed aggregation; on a mesh with structured topology
                          (one partition) index-space geometric transfers with
                          Galerkin coarse operators */
+#define TV_PC_AUX 3   /* auxiliary-space algebraic multigrid for DG1 temperature on unstructured meshes, one
+                         partition (csrc/tv_umdg_aux.hip, tv_amg.cpp aux_setup): level 0 the DG space with a
+                         cell-block Jacobi smoother (the inverted diagonal blocks of J(T)), level 1 the CG1
+                         space of the same mesh (vertex sums down, injection up, the CG1 cell operator
+                         M + dt alpha K), below it TV_PC_AMG's aggregation hierarchy; additive at level 0,
+                         z = omega0 B^-1 r + P V_1(P^T r).  CG1 temperature: TV_PC_AMG; box meshes: TV_PC_GMG;
+                         no Dirichlet mode (tv_set_dirichlet: TV_ERR_STATE) */
 
 /* Model semantics.  REFERENCE reproduces the reference as it runs, quirks
  * included.  PAPER (opt-in, never the default) applies
@@ -322,7 +333,9 @@ int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params*
  * for the temperature and for the stress, all four pairings (main.py runs DG1
  * temperature with CG1 stress); DG dofs are numbered cell-major, dof = cell *
  * 2^dim + local vertex, as on the box meshes.  Jacobi-PCG in the KSPCG form;
- * TV_PC_AMG with a CG1 temperature only (TV_ERR_ARG with DG1 temperature).  The
+ * TV_PC_AMG with a CG1 temperature only (TV_ERR_ARG with DG1 temperature),
+ * TV_PC_AUX with a DG1 temperature only (TV_ERR_ARG with CG1 temperature; a
+ * cell block that is not positive definite: TV_ERR_ARG).  The
  * Dirichlet mode acts on a CG1 temperature; with DG1 it is accepted and has no
  * effect, as on the box meshes. */
 int tv_create_unstructured(const tv_umesh_desc* mesh, const tv_fe_config* fe, const tv_params* params,
@@ -430,8 +443,9 @@ int tv_residual(void* ctx, const double* T_dev, double* F_dev);     /* F(T; T_pr
 int tv_jacobian_apply(void* ctx, const double* x_dev, double* y_dev); /* J(T)·x      */
 int tv_jacobian_diag(void* ctx, double* d_dev);                       /* diag J(T)   */
 /* z = B r with the context's preconditioner at the current T (tv_options.
- * preconditioner): Jacobi z = r / diag J(T), or one V-cycle of the geometric
- * multigrid -- exactly the operator the Krylov solve applies (the PC setup of
+ * preconditioner): Jacobi z = r / diag J(T), or one V-cycle of the geometric,
+ * the algebraic (TV_PC_AMG) or the auxiliary-space (TV_PC_AUX: the DG level's
+ * cell-block smoothing included) multigrid -- exactly the operator the Krylov solve applies (the PC setup of
  * the current T included).  Uses the solver's work vectors.  On a partition of
  * a box mesh (owned dofs in and out) the call is collective: every rank calls
  * it, through its communicator (the distributed or the per-slab V-cycle,
@@ -675,7 +689,10 @@ int tv_comm_time(void* ctx, int pattern, int reps, double* us_per_call);
  * 2 = residual, 3 = fused PCG matvec (p <- z + b p; w <- J p; p.w),
  * 4 = PCG vector update, 10 = Jacobian apply with the 256 MiB Infinity Cache
  * flushed (512 MiB write) before every launch, events around the launch alone,
- * the MEDIAN over the reps, 11 = one GMG V-cycle.  Launch audit, 12-17: `reps`
+ * the MEDIAN over the reps, 11 = one GMG / AMG V-cycle (TV_PC_AUX: with the DG
+ * level's pre-smoothing x0 = omega0 B^-1 r, which a solve runs inside its
+ * update launch), 18 = TV_PC_AUX's per-Newton refresh of the block inverses
+ * of the cells with an exterior facet.  Launch audit, 12-17: `reps`
  * back-to-back launches queued behind a spin kernel (timed as the GPU runs them,
  * not at the host's enqueue rate), events around the chain: 12 an empty
  * one-thread kernel, 13 the solver-state upload kernel, 14 the one-block

@@ -2,7 +2,7 @@
 coupled step on a distorted plate, with the CG1 path of the same mesh in the
 same run for context.
 
-    python tools/umdg_bench.py [--cells 96 96 24] [--steps 5] [--warmup 2] [--reps 21]
+    python tools/umdg_bench.py [--cells 96 96 24] [--steps 5] [--warmup 2] [--reps 21] [--pc jacobi|aux]
 
 Per family pairing (DG/CG: csrc/tv_umdg.hip, CG/CG: csrc/tv_um.hip, SELL-64):
   * J x with the Infinity Cache flushed before every launch, the median over
@@ -15,6 +15,15 @@ The plate keeps its plane-by-plane numbering with two vertex ids swapped, so
 the CG path streams its SELL-64 operator (on a structured numbering it would
 switch to its half stencils) and both paths see the locality of a generated
 mesh; --numbering shuffled removes it.  One JSON to profiles/umdg_bench.json.
+
+--pc aux: the DG/CG plate both ways in one process -- point Jacobi (the
+yardstick: the same code path as without the option) and the auxiliary-space
+multigrid (TV_PC_AUX, csrc/tv_umdg_aux.hip), --rounds times each, alternating,
+every run a fresh context stepping from the same initial condition.  The aux
+records add the cycle's time and algorithmic bytes (tv_time_kernel /
+tv_kernel_bytes 11: the DG level's pre-smoothing, the transfers and the
+levels below), the per-Newton refresh of the boundary cells' block inverses
+(id 18) and the creation time (hierarchy and block inverses included).
 """
 import argparse
 import ctypes as C
@@ -32,13 +41,14 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0
 
 
-def run(mesh, fam_T, a):
+def run(mesh, fam_T, a, pc="jacobi"):
     from oracle.tv_oracle import MAIN_MODEL_PARAMS
     from tvfem import _native as N
     from tvfem.problem import ThermoViscoProblem
     cfg = {"T": {"element": fam_T, "degree": 1}, "sigma": {"element": "CG", "degree": 1}}
     t0 = time.perf_counter()
-    p = ThermoViscoProblem(mesh, (0.0, 1.0), 0.1, cfg, dict(MAIN_MODEL_PARAMS), verbose=False, write_output=False)
+    p = ThermoViscoProblem(mesh, (0.0, 1.0), 0.1, cfg, dict(MAIN_MODEL_PARAMS), verbose=False, write_output=False,
+                           preconditioner=pc)
     setup_s = time.perf_counter() - t0
     p.setup()
     lib, ctx = p._lib, p._ctx
@@ -69,10 +79,18 @@ def run(mesh, fam_T, a):
              "bytes": jx["bytes"] - 16.0 * p.num_dofs(0)[0] + by.value}
     fused["GBps_in_solve"] = fused["bytes"] / (live.value * 1e-3) / 1e9 if live.value > 0 else None
     n = p.num_dofs(0)[0]
+    extra = {}
+    if pc == "aux":
+        for key, kid in (("cycle", 11), ("block_refresh", 18)):
+            N.check(lib.tv_time_kernel(ctx, kid, a.reps, C.byref(ms)), ctx)
+            N.check(lib.tv_kernel_bytes(ctx, kid, C.byref(by)), ctx)
+            extra[key] = {"ms_back_to_back": ms.value, "bytes": by.value,
+                          "GBps": by.value / (ms.value * 1e-3) / 1e9 if ms.value > 0 else None}
     p.close()
-    return {"T_family": fam_T, "sigma_family": "CG", "T_dofs": n, "create_s": setup_s, "ms_per_step": step_ms,
-            "newton_its_per_step": float(np.mean([i[0] for i in its])),
-            "krylov_its_per_step": float(np.mean([i[1] for i in its])), "jacobian_apply": jx, "fused_matvec": fused}
+    return {"T_family": fam_T, "sigma_family": "CG", "preconditioner": pc, "T_dofs": n, "create_s": setup_s,
+            "ms_per_step": step_ms, "newton_its_per_step": float(np.mean([i[0] for i in its])),
+            "krylov_its_per_step": float(np.mean([i[1] for i in its])), "jacobian_apply": jx, "fused_matvec": fused,
+            **extra}
 
 
 def main():
@@ -91,6 +109,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reps", type=int, default=21, help="timed launches per isolated kernel (median / mean)")
     ap.add_argument("--only", choices=["DG", "CG"], default=None, help="time one temperature family only")
+    ap.add_argument("--pc", choices=["jacobi", "aux"], default="jacobi",
+                    help="aux: the DG/CG plate with point Jacobi and with the auxiliary-space multigrid, alternating")
+    ap.add_argument("--rounds", type=int, default=2, help="--pc aux: runs per preconditioner")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "umdg_bench.json"))
     a = ap.parse_args()
     from tvfem import distorted_box_mesh
@@ -104,7 +125,19 @@ def main():
     res = {"mesh": {"cells": a.cells, "lengths": a.lengths, "n_cells": mesh.num_cells,
                     "n_vertices": mesh.num_vertices, "distortion": f"amp {a.amp:g}, seed 0", "numbering": a.numbering},
            "steps": a.steps, "warmup": a.warmup, "reps": a.reps, "hbm_peak_GBps": HBM_PEAK_GBS,
-           "runs": [run(mesh, f, a) for f in ("DG", "CG") if a.only in (None, f)]}
+           "runs": [run(mesh, f, a) for f in ("DG", "CG") if a.only in (None, f) and not (a.pc == "aux" and f == "DG")]}
+    if a.pc == "aux" and a.only in (None, "DG"):
+        # the yardstick is the Jacobi step of this very process; rounds alternate so that drift hits both alike
+        pairs = [[run(mesh, "DG", a, pc) for pc in ("jacobi", "aux")] for _ in range(max(1, a.rounds))]
+        by_pc = {pc: [r[k] for r in pairs] for k, pc in enumerate(("jacobi", "aux"))}
+        best = {pc: min(rs, key=lambda r: r["ms_per_step"]) for pc, rs in by_pc.items()}
+        for pc in ("jacobi", "aux"):
+            best[pc]["ms_per_step_rounds"] = [r["ms_per_step"] for r in by_pc[pc]]
+            best[pc]["create_s_rounds"] = [r["create_s"] for r in by_pc[pc]]
+        res["runs"] = [best["jacobi"], best["aux"]] + res["runs"]
+        res["aux_vs_jacobi"] = {
+            "step_time_ratio": best["aux"]["ms_per_step"] / best["jacobi"]["ms_per_step"],
+            "krylov_ratio": best["aux"]["krylov_its_per_step"] / best["jacobi"]["krylov_its_per_step"]}
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)
