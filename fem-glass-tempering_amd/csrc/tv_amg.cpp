@@ -616,7 +616,7 @@ static int amg_build(Ctx* c, Csr A, int64_t row0, int64_t nrow, const int64_t* g
   HIPC(hipMemset(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT)));
   c->amg_on = true;
   c->mg_on = true;
-  c->mg_omega0 = 0.0;  // the level-0 weight: lazily, at the temperature of the first solve (mg_dg_weight)
+  c->mg_omega0 = 0.0;  // the level-0 weight: lazily, at the temperature of the first solve (level0_weight)
   return TV_OK;
 }
 
@@ -776,7 +776,7 @@ int aux_setup(Ctx* c) {
     for (double** v : {&L.b, &L.x, &L.w})
       if (int e = amg_alloc(c, (size_t)nv, v)) return e;
   }
-  c->aux_on = true;
+  c->smoother0 = Smoother0::AUX_BLOCK;
   return amg_build(c, std::move(A), 0, nv);
 }
 
@@ -897,18 +897,20 @@ static const double* amg_level(Ctx* c, size_t l) {
   return L.w;
 }
 
-// z = omega0 D^-1 r (x0 = c->mgx, formed by k_mg_update) + P_0 V_1(P_0^T r),
+// z = omega0 B^-1 r (x0 = c->mgx, formed by level0_update) + P_0 V_1(P_0^T r),
 // with the (z.z, z.r) records and the KSPCG tail
 int amg_apply0(Ctx* c, const RedTail* tail) {
   AmgLevel& L1 = c->amg[0];
-  if (c->aux_on) {  // DG level 0 over the CG1 level: vertex sums down, injection up (tv_umdg_aux.hip)
+  // the auxiliary space: DG level 0 over the CG1 level, vertex sums down, injection up (tv_umdg_aux.hip)
+  if (c->smoother0 == Smoother0::AUX_BLOCK) {
     launch_umdg_aux_restrict(c->aux, c->st, c->r, L1.dinv, L1.omega, L1.b, L1.x, c->stream);
     const double* x1 = amg_level(c, 1);
-    return launch_umdg_aux_prolong0(c->udg, c->aux, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
+    launch_umdg_aux_prolong0(c->udg, c->aux, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
+    return TV_OK;
   }
   if (c->n_parts > 1) {  // the partial restriction of the owned fine rows, summed over the ranks
     launch_amg_restrict(L1.R, c->st, c->r, nullptr, nullptr, 0.0, L1.b, nullptr, c->stream);
-    if (int e = allreduce_vec(c, L1.b, L1.n)) return -e;
+    if (int e = allreduce_vec(c, L1.b, L1.n)) return e;
     launch_mg_jacobi(L1.n, c->st, L1.b, nullptr, nullptr, L1.dinv, L1.omega, L1.x, 0, c->stream);
   } else if (L1.geo0) {
     launch_geo_restrict0(L1.gfine, L1.gcoarse, c->st, c->r, L1.dinv, L1.omega, L1.b, L1.x, c->stream);
@@ -916,9 +918,9 @@ int amg_apply0(Ctx* c, const RedTail* tail) {
     launch_amg_restrict(L1.R, c->st, c->r, nullptr, L1.dinv, L1.omega, L1.b, L1.x, c->stream);
   }
   const double* x1 = amg_level(c, 1);
-  if (L1.geo0)
-    return launch_geo_prolong0(L1.gfine, L1.gcoarse, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
-  return launch_amg_prolong0(L1.P, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
+  if (L1.geo0) launch_geo_prolong0(L1.gfine, L1.gcoarse, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
+  else launch_amg_prolong0(L1.P, c->st, x1, c->mgx, c->r, c->z, c->partials, tail, c->stream);
+  return TV_OK;
 }
 
 // algorithmic bytes of one V-cycle (tv_kernel_bytes 11): the stored entries
@@ -933,7 +935,7 @@ double amg_cycle_bytes(const Ctx* c) {
   const double t0 = L1.geo0 ? 0.0 : 8.0;
   double b = t0 * (double)L1.r_nnz + 8.0 * n0 + 24.0 * (double)L1.n;
   b += t0 * (double)L1.p_nnz + 8.0 * (double)L1.n + 24.0 * n0;
-  if (c->aux_on) {
+  if (c->smoother0 == Smoother0::AUX_BLOCK) {
     // the auxiliary-space cycle as tv_time_kernel runs it (with its pre-smoothing x0 = omega0 B^-1 r): the
     // packed block inverses, r in and x0 out, and the two transfers' index tables (no stored values)
     const double nl = (double)(1 << c->dim);

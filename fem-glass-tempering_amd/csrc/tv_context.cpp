@@ -1333,7 +1333,8 @@ int tv_set_dirichlet(void* ctx, int enable, double value) {
     return c->fail(TV_ERR_STATE, "Dirichlet condition: only with model_mode = TV_MODEL_PAPER (the reference's "
                                  "own path cannot run, ThermoViscoProblem.py:236-243)");
   if (enable && c->amg_on)
-    return c->fail(TV_ERR_STATE, c->aux_on ? "Dirichlet condition: not with TV_PC_AUX (Jacobi or the box multigrid)"
+    return c->fail(TV_ERR_STATE, c->smoother0 == Smoother0::AUX_BLOCK
+                                     ? "Dirichlet condition: not with TV_PC_AUX (Jacobi or the box multigrid)"
                                            : "Dirichlet condition: not with TV_PC_AMG (Jacobi or the box multigrid)");
   hipSetDevice(c->device);
   c->dir_on = enable != 0;

@@ -87,6 +87,13 @@ struct AmgLevel {
   double *dinv = nullptr, *b = nullptr, *x = nullptr, *w = nullptr;
 };
 
+// The smoother B of multigrid level 0 (POINT: the Jacobi preconditioner too):
+// point Jacobi dinv; the cell blocks of a DG1 box built from dggface (set by
+// mg_setup); the packed cell-block inverses of UmDgAux (set by aux_setup).
+// What B does is spelled out in level0_setup / _smooth / _update only; the
+// cycles ask for the kind where the hierarchy below level 0 differs.
+enum class Smoother0 { POINT, DG_BLOCK, AUX_BLOCK };
+
 struct Ctx {
   std::string err;
   int device = 0;
@@ -155,7 +162,7 @@ struct Ctx {
   Output* out = nullptr;  // time-series output (tv_output_*)
   // geometric multigrid (options.preconditioner = TV_PC_GMG): levels 1.. (level 0 = cg)
   bool mg_on = false;
-  bool mg_dg = false;       // DG1 level 0 over the CG1 hierarchy of the same box
+  Smoother0 smoother0 = Smoother0::POINT;
   std::vector<MgLevel> mg;
   double mg_omega0 = 0.0;
   double* mgx = nullptr;    // level-0 V-cycle iterate
@@ -191,7 +198,6 @@ struct Ctx {
   std::vector<void*> amg_bufs;
   // auxiliary-space multigrid (TV_PC_AUX: um_dg, tv_amg.cpp aux_setup): amg[0] is the CG1 space of the
   // mesh (A = its cell operator V, no stored transfers), amg[1..] the aggregation hierarchy below it
-  bool aux_on = false;
   UmDgAux aux{};
   // partitioned unstructured mesh (tv_create_unstructured_part): owned vertices
   // first, ghosts grouped by owner; per neighbour k: the ghosts received from
@@ -305,7 +311,7 @@ int aux_setup(Ctx* c);       // TV_PC_AUX: the DG level's tables and block inver
 void aux_refresh(Ctx* c, const double* T);
 // x = omega B^-1 b over the DG dofs (x may be b)
 void aux_smooth(Ctx* c, const PcgState* st, const double* b, double omega, double* x);
-int amg_apply0(Ctx* c, const RedTail* tail);
+int amg_apply0(Ctx* c, const RedTail* tail);  // a status
 double amg_cycle_bytes(const Ctx* c);
 
 // ---- tv_context.cpp ----
@@ -399,9 +405,23 @@ void launch_bc_mask(Ctx* c, double* dinv);  // dinv = 0 on the Dirichlet-constra
 
 // ---- tv_mgsolve.cpp ----
 int mg_setup(Ctx* c);
+// per Newton iteration: T down the hierarchy and the coarse Jacobi diagonals (one partition or slabs)
 int mg_prepare(Ctx* c, const double* T);
-int mg_dg_weight(Ctx* c, const double* T);
-int mg_apply0(Ctx* c, const double* T, const RedTail* tail);
+// level 0's smoother weight mg_omega0 where it is estimated (DG_BLOCK, AMG): at the first solve, at its T
+int level0_weight(Ctx* c, const double* T);
+// B at T, the per-Newton preconditioner set-up (dinv_fresh: the residual's boundary pass wrote dinv already)
+void level0_setup(Ctx* c, const double* T, bool dinv_fresh = false);
+// x = omega B^-1 b on [off, off + n) (the block kinds: every cell; x may be b)
+void level0_smooth(Ctx* c, const PcgState* st, const double* b, double omega, double* x, int64_t off, int64_t n);
+// the KSPCG update on [off, off + n): r <- r - a w, dx, x0 <- omega0 B^-1 r; init: x0 only
+void level0_update(Ctx* c, int it, bool init, int64_t off, int64_t n, const double* lag = nullptr,
+                   unsigned* counter = nullptr);
+// the start of a partitioned multigrid solve: the hierarchy at T (AMG: level 0's weight), dinv's ghosts
+// under Dirichlet, level 0's restriction mask
+int mg_dist_begin(Ctx* c, const double* T);
+// z <- V(r) from x0 in c->mgx, with the (z.z, z.r) records and the tail: the distributed CG-box cycle,
+// the local box cycle or the algebraic one.  A status.
+int mg_cycle(Ctx* c, const double* T, const RedTail* tail);
 // post: queue the Newton iteration's post-solve group (launch_post_group, ||dx||
 // copied to h_sums, evn[slot] recorded) behind every batch, gated on the device state
 int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post = false);
@@ -427,8 +447,8 @@ int mg_upload(Ctx* c, MgLevel& L, const std::vector<T>& h, const T** out) {
 // ---- tv_mgdist.cpp (GMG on a slab-partitioned box) ----
 int mg_setup_dist(Ctx* c);
 int pcg_solve_mg_dist(Ctx* c, const double* T, int* its, int* reason, bool post = false);
-int mg_prepare_dist(Ctx* c, const double* T);
+int mg_prepare_dist(Ctx* c, const double* T);  // slabs of a CG1 box (mg_prepare)
 void fine_window(const Ctx* c, int64_t* off, int64_t* n);
-int mg_apply0_dist(Ctx* c, const double* T, const RedTail* tail);
+int mg_cycle_dist(Ctx* c, const double* T, const RedTail* tail);  // slabs of a CG1 box (mg_cycle)
 
 }  // namespace tv

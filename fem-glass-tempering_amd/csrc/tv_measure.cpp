@@ -89,8 +89,9 @@ int tv_kernel_bytes(void* ctx, int kernel, double* bytes) {
       // DG: J x (16) + the cell-block post-smoothing (x0, r, w in, z out: 32)
       // (a fused residual restriction, RRArgs: no J x0, the restriction reads r
       // and x0 -- 16 B instead of 32; the facet terms it needs touch the faces only)
-      const bool rr0 = !c->mg_dg && !c->mg.empty() && c->mg[0].rr.on;
-      double b = (c->mg_dg ? 16.0 + 16 + 16 + 16 + 32 : (rr0 ? 0.0 : 16.0) + 16 + 16 + 24) * n;
+      const bool dg = c->smoother0 == Smoother0::DG_BLOCK;
+      const bool rr0 = !dg && !c->mg.empty() && c->mg[0].rr.on;
+      double b = (dg ? 16.0 + 16 + 16 + 16 + 32 : (rr0 ? 0.0 : 16.0) + 16 + 16 + 24) * n;
       for (size_t l = 0; l < c->mg.size(); ++l) {
         const double nl = (double)c->mg[l].n;
         b += 24.0 * nl;  // the restriction's outputs b, x (pre-smoothing) and the dinv it reads
@@ -102,7 +103,8 @@ int tv_kernel_bytes(void* ctx, int kernel, double* bytes) {
       break;
     }
     case 18: {  // TV_PC_AUX: the per-Newton block refresh -- the lower triangle of slot 0 in, the packed inverse out
-      if (!c->aux_on) return c->fail(TV_ERR_ARG, "kernel 18: preconditioner TV_PC_AUX not enabled");
+      if (c->smoother0 != Smoother0::AUX_BLOCK)
+        return c->fail(TV_ERR_ARG, "kernel 18: preconditioner TV_PC_AUX not enabled");
       const double nl = (double)(1 << c->dim);
       *bytes = (16.0 * (nl * (nl + 1.0) / 2.0) + 8.0 * nl + 4.0 * (2.0 * c->dim + 1.0)) * (double)c->aux.nbc;
       break;
@@ -140,24 +142,21 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
     PcgState h{};
     h.max_it = 1 << 30;
     HIPC(hipMemcpyAsync(c->st, &h, sizeof(PcgState), hipMemcpyHostToDevice, c->stream));
-    if (c->n_parts > 1) {
-      if (int e = mg_prepare_dist(c, c->f[TV_F_T].ptr)) return e;
-    } else {
-      if (int e = mg_prepare(c, c->f[TV_F_T].ptr)) return e;
-    }
-    if (int e = mg_dg_weight(c, c->f[TV_F_T].ptr)) return e;
-    if (c->aux_on) aux_refresh(c, c->f[TV_F_T].ptr);  // the cell blocks at the current T, as a Newton iteration sets them
+    if (int e = mg_prepare(c, c->f[TV_F_T].ptr)) return e;
+    if (int e = level0_weight(c, c->f[TV_F_T].ptr)) return e;
+    // the cell blocks at the current T, as a Newton iteration sets them (dinv, dggface: as the last solve left them)
+    if (c->smoother0 == Smoother0::AUX_BLOCK) level0_setup(c, c->f[TV_F_T].ptr);
   }
-  if (kernel == 18 && !c->aux_on) return c->fail(TV_ERR_ARG, "kernel 18: preconditioner TV_PC_AUX not enabled");
+  if (kernel == 18 && c->smoother0 != Smoother0::AUX_BLOCK)
+    return c->fail(TV_ERR_ARG, "kernel 18: preconditioner TV_PC_AUX not enabled");
   auto one = [&]() -> int {
     int np = 0;
     switch (kernel) {
-      case 11:  // partitioned: the distributed V-cycle, its exchanges included (every rank calls this)
-        if (c->n_parts > 1) return mg_apply0_dist(c, c->f[TV_F_T].ptr, nullptr);
-        // the auxiliary-space cycle with its pre-smoothing x0 = omega0 B^-1 r (in a solve: the update launch)
-        if (c->aux_on) aux_smooth(c, c->st, c->r, c->mg_omega0, c->mgx);
-        np = mg_apply0(c, c->f[TV_F_T].ptr, nullptr);
-        return np < 0 ? -np : TV_OK;
+      case 11:  // partitioned: the cycle's exchanges included (every rank calls this)
+        // the auxiliary-space cycle, and only it, is timed with its pre-smoothing x0 = omega0 B^-1 r
+        // (in a solve: the update launch), as amg_cycle_bytes counts it
+        if (c->smoother0 == Smoother0::AUX_BLOCK) level0_smooth(c, c->st, c->r, c->mg_omega0, c->mgx, 0, c->nT);
+        return mg_cycle(c, c->f[TV_F_T].ptr, nullptr);
       case 0: jx(); return TV_OK;
       case 18: aux_refresh(c, c->f[TV_F_T].ptr); return TV_OK;
       case 1: return visco(c, false);
@@ -222,7 +221,8 @@ int tv_time_kernel(void* ctx, int kernel, int reps, double* ms) {
     //   12 an empty one-thread kernel        13 k_set_state (one thread, 160-B argument)
     //   14 the one-block reduce + KSPCG logic 15 k_mg_jacobi on the coarsest GMG level
     //   16 J x on GMG level 1 (march)        17 J x on the fine grid (march + faces)
-    if ((kernel >= 15 && kernel <= 16) && (!c->mg_on || c->mg.empty() || c->amg_on || c->mg_dg))
+    if ((kernel >= 15 && kernel <= 16) &&
+        (!c->mg_on || c->mg.empty() || c->amg_on || c->smoother0 == Smoother0::DG_BLOCK))
       return c->fail(TV_ERR_ARG, "kernel ids 15-16: CG GMG levels required");
     if (kernel == 17 && (c->um || c->fam_T != TV_CG)) return c->fail(TV_ERR_ARG, "kernel 17: CG box mesh");
     PcgState h{};

@@ -361,7 +361,6 @@ int mg_setup_dist(Ctx* c) {
 // level: each rank injects its own planes into a zeroed vector, summed over
 // the ranks; below it, injected locally) and the Jacobi diagonals
 int mg_prepare_dist(Ctx* c, const double* T) {
-  if (c->mg_dg) return mg_prepare(c, T);  // a DG1 slab: level 1 onwards replicated (mg_setup)
   const double* Tf = T;
   for (size_t l = 1; l <= c->mg.size(); ++l) {
     MgLevel& L = c->mg[l - 1];
@@ -387,11 +386,7 @@ int mg_prepare_dist(Ctx* c, const double* T) {
 // KSPCG update); on exit z (owned) = the V-cycle applied to r and the (z.z,
 // z.r) records reduced into c->sums by the tail (kind 0: the all-reduce and
 // the KSPCG logic follow).  Returns a status.
-int mg_apply0_dist(Ctx* c, const double* T, const RedTail* tail) {
-  if (c->amg_on || c->mg_dg) {  // the agglomerated algebraic cycle (tv_amg.cpp); a DG1 slab (tv_mgsolve.cpp)
-    const int r = c->amg_on ? amg_apply0(c, tail) : mg_apply0(c, T, tail);
-    return r < 0 ? -r : TV_OK;
-  }
+int mg_cycle_dist(Ctx* c, const double* T, const RedTail* tail) {
   hipStream_t s = c->stream;
   const size_t L = c->mg.size() + 1;  // levels incl. 0
   const size_t A = (size_t)c->mg_A;
@@ -465,15 +460,6 @@ int mg_apply0_dist(Ctx* c, const double* T, const RedTail* tail) {
   return TV_OK;
 }
 
-namespace {
-
-// fold: the box march path -- the scalar logic after each all-reduce runs
-// lagged inside the next launch (lagged_state) instead of as a one-thread
-// launch: the beta / convergence logic of the previous iteration's closing
-// group inside this iteration's fused matvec (lag3), the alpha logic inside
-// the update.  Every rank forms the same state from the same all-reduced sums.
-}  // namespace
-
 // the level-0 nodes a partition's pointwise V-cycle kernels cover: the owned
 // ones, or on a deep-ghost slab the write window (every ghost plane but the
 // outermost: x0 = omega D^-1 r is needed there, so J x0 is right one plane out)
@@ -488,9 +474,12 @@ void fine_window(const Ctx* c, int64_t* off, int64_t* n) {
   *n = plane * (c->cg.w_end - c->cg.w_begin);
 }
 
-namespace {
-
-int mg_iteration_dist(Ctx* c, const double* T, int it, bool fold, bool lag3) {
+// fold: the box march path -- the scalar logic after each all-reduce runs
+// lagged inside the next launch (lagged_state) instead of as a one-thread
+// launch: the beta / convergence logic of the previous iteration's closing
+// group inside this iteration's fused matvec (lag3), the alpha logic inside
+// the update.  Every rank forms the same state from the same all-reduced sums.
+static int mg_iteration_dist(Ctx* c, const double* T, int it, bool fold, bool lag3) {
   int64_t off, n;
   fine_window(c, &off, &n);
   RedTail t1{c->counters, c->partials, c->sums, c->st, 0, iter_stamp(c, it)};
@@ -508,20 +497,11 @@ int mg_iteration_dist(Ctx* c, const double* T, int it, bool fold, bool lag3) {
     if (fold) lag2 = true;
     else launch_logic(c->st, c->sums, 2, c->stream);  // alpha
   }
-  if (c->dggface) {  // a DG1 slab: the cell-block update (the alpha logic ran above: no fold on DG)
-    launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it,
-                      0, c->stream);
-  } else {
-    const FaceAdd fa = c->um ? FaceAdd{} : cg_face_add(c->cg, off);  // unstructured: w is complete
-    launch_mg_update(n, c->st, c->pA + off, c->pB + off, c->w + off, &fa, c->dinv + off, c->mg_omega0, c->r + off,
-                     c->f[TV_F_DX].ptr + off, c->mgx + off, it, 0, c->stream, lag2 ? c->sums : nullptr,
-                     lag2 ? c->counters + kUpdateCounter : nullptr);
-  }
+  // (a DG1 slab: the alpha logic ran above, no fold on DG)
+  level0_update(c, it, false, off, n, lag2 ? c->sums : nullptr, lag2 ? c->counters + kUpdateCounter : nullptr);
   RedTail t2{c->counters + kTailCounters, c->partials, c->sums, c->st, 0, nullptr};
-  return mg_apply0_dist(c, T, &t2);
+  return mg_cycle(c, T, &t2);
 }
-
-}  // namespace
 
 // The single-reduction (Chronopoulos-Gear) form of the GMG-preconditioned CG
 // on deep-ghost slabs (c->mg_cgs): per iteration the update (k_mg_update_cgs:
@@ -537,18 +517,14 @@ static int pcg_solve_mg_dist_cgs(Ctx* c, const double* T, int* its, int* reason,
   int64_t woff, nwin;
   fine_window(c, &woff, &nwin);
   solve_begin(c, c->solve_gate);
-  if (int e = mg_prepare_dist(c, T)) return e;
-  if (c->dir_on)
-    if (int e = halo(c, c->dinv)) return e;
-  if (c->mg_mask0) launch_mg_ownmask(c->nT, off, off + n, c->dir_on ? c->dinv : nullptr, c->mg_mask0, c->stream);
-  launch_mg_update(nwin, c->st, c->pA + woff, c->pB + woff, c->w + woff, nullptr, c->dinv + woff, c->mg_omega0,
-                   c->r + woff, c->f[TV_F_DX].ptr + woff, c->mgx + woff, 0, 1, c->stream);  // x0 <- omega dinv r
+  if (int e = mg_dist_begin(c, T)) return e;
+  level0_update(c, 0, true, woff, nwin);  // x0 <- omega dinv r
   double* u = c->w;  // A z, completed on the ghost planes by the closing group
   int pending = 0;   // logic kind of the last closing group still to run (inside the next update)
   // V-cycle (z, z.z, z.r -> sums[0..1]), u = A z (z.u -> sums[2]), the closing group
   auto half = [&](int it) -> int {
     RedTail tz{c->counters + kTailCounters, c->partials, c->sums, c->st, 0, nullptr};
-    if (int e = mg_apply0_dist(c, T, &tz)) return e;
+    if (int e = mg_cycle(c, T, &tz)) return e;
     RedTail tu{c->counters, c->partials, c->sums + 2, c->st, 0, iter_stamp(c, it)};
     if (!launch_cg_japply_tail(c->cg, T, c->z, u, c->st, c->partials, &tu, c->stream))
       return c->fail(TV_ERR_STATE, "single-reduction GMG needs the marching matvec (internal)");
@@ -589,23 +565,9 @@ int pcg_solve_mg_dist(Ctx* c, const double* T, int* its, int* reason, bool post)
   int64_t woff, nwin;
   fine_window(c, &woff, &nwin);
   solve_begin(c, c->solve_gate);
-  if (c->amg_on) {  // the algebraic hierarchy is T-independent; level 0's weight at the first solve
-    if (int e = mg_dg_weight(c, T)) return e;
-  } else if (int e = mg_prepare_dist(c, T)) {
-    return e;
-  }
-  if (c->dir_on)  // the prolongation masks level 0's ghost planes with dinv too
-    if (int e = halo(c, c->dinv)) return e;
-  if (c->mg_mask0)  // level 0's restriction mask: owned nodes, Dirichlet rows out
-    launch_mg_ownmask(c->nT, off, off + n, c->dir_on ? c->dinv : nullptr, c->mg_mask0, c->stream);
-  if (c->dggface) {  // a DG1 slab: x0 <- omega B^-1 r over the owned cells
-    if (int e = mg_dg_weight(c, T)) return e;
-    launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0, 1,
-                      c->stream);
-  } else {
-    launch_mg_update(nwin, c->st, c->pA + woff, c->pB + woff, c->w + woff, nullptr, c->dinv + woff, c->mg_omega0,
-                     c->r + woff, c->f[TV_F_DX].ptr + woff, c->mgx + woff, 0, 1, c->stream);  // x0 <- omega dinv r
-  }
+  if (int e = mg_dist_begin(c, T)) return e;
+  if (int e = level0_weight(c, T)) return e;  // a DG1 slab's, at the first solve
+  level0_update(c, 0, true, woff, nwin);  // x0 <- omega0 B^-1 r over the write window (DG: the owned cells)
   // the three collectives of an iteration close it: the (z.z, z.r) all-reduce
   // + KSPCG logic, and the ghost planes of z for the next fused matvec
   // the lagged logic needs the box march's fused matvec (not the unstructured
@@ -624,7 +586,7 @@ int pcg_solve_mg_dist(Ctx* c, const double* T, int* its, int* reason, bool post)
   };
   {
     RedTail t0{c->counters + kTailCounters, c->partials, c->sums, c->st, 0, nullptr};
-    if (int e = mg_apply0_dist(c, T, &t0)) return e;
+    if (int e = mg_cycle(c, T, &t0)) return e;
     if (int e = close(1, false)) return e;  // dp, beta (KSPCG init)
   }
   auto iterate = [&](int it, int b, int nb) -> int {

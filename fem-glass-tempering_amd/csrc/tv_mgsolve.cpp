@@ -48,7 +48,6 @@ double mg_gershgorin(const std::vector<double> (&X)[3], double dt_alpha) {
 
 double mg_omega(double b) { return 2.0 / (1.1 * b); }
 
-// the hierarchy below the fine grid (single partition, 3D CG1 marching path)
 // the CG1 level of the box given by X (single partition), its vectors and weight
 int mg_add_cg_level(Ctx* c, const std::vector<double> (&X)[3], double da) {
   c->mg.emplace_back();
@@ -61,10 +60,56 @@ int mg_add_cg_level(Ctx* c, const std::vector<double> (&X)[3], double da) {
   return TV_OK;
 }
 
-// lambda_max(B^-1 J) of the DG1 operator by power iteration, B the cell blocks;
-// SIPG rows have no closed-form
-// Gershgorin bound here.  The smoother takes it with a 21 % margin
-int mg_dg_lambda(Ctx* c, const double* T, double* lam) {
+// ---- level 0's smoother B (Smoother0): what each kind launches, here only ----
+void level0_setup(Ctx* c, const double* T, bool dinv_fresh) {
+  switch (c->smoother0) {
+    case Smoother0::DG_BLOCK: return;  // the facet means of dg(T) are launched by mg_prepare, with level 1's T
+    case Smoother0::AUX_BLOCK: aux_refresh(c, T); return;  // the blocks of the cells with an exterior facet follow T
+    case Smoother0::POINT: break;
+  }
+  if (!c->um && c->fam_T == TV_CG) {
+    // the box march path: the T-independent interior of dinv is written once; then the boundary nodes only
+    if (!dinv_fresh) launch_cg_diag(c->cg, T, c->dinv, 1, c->stream, c->dinv_interior);
+    c->dinv_interior = true;
+  } else {
+    op_diag(c, T, c->dinv, 1);
+  }
+}
+
+void level0_smooth(Ctx* c, const PcgState* st, const double* b, double omega, double* x, int64_t off, int64_t n) {
+  switch (c->smoother0) {
+    case Smoother0::POINT:
+      launch_mg_jacobi(n, st, b + off, nullptr, nullptr, c->dinv + off, omega, x + off, 0, c->stream);
+      return;
+    case Smoother0::DG_BLOCK: launch_dg_bsmooth(c->dg, st, b, nullptr, c->dggface, omega, x, 0, c->stream); return;
+    case Smoother0::AUX_BLOCK: aux_smooth(c, st, b, omega, x); return;
+  }
+}
+
+void level0_update(Ctx* c, int it, bool init, int64_t off, int64_t n, const double* lag, unsigned* counter) {
+  double* dx = c->f[TV_F_DX].ptr;
+  switch (c->smoother0) {
+    case Smoother0::POINT: {
+      // w lacks the facet terms of the faces along the march on a CG box only (DG, unstructured: complete)
+      const FaceAdd fa = (!init && !c->um && c->fam_T == TV_CG) ? cg_face_add(c->cg, off) : FaceAdd{};
+      launch_mg_update(n, c->st, c->pA + off, c->pB + off, c->w + off, init ? nullptr : &fa, c->dinv + off,
+                       c->mg_omega0, c->r + off, dx + off, c->mgx + off, it, init, c->stream, lag, counter);
+      return;
+    }
+    case Smoother0::DG_BLOCK:  // the owned cells (no lagged logic on DG)
+      launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, dx, c->mgx, it, init,
+                        c->stream);
+      return;
+    case Smoother0::AUX_BLOCK:
+      launch_umdg_aux_update(c->udg, c->aux, c->st, c->pA, c->pB, c->w, c->mg_omega0, c->r, dx, c->mgx, it, init,
+                             c->stream);
+      return;
+  }
+}
+
+// lambda_max(B^-1 J) of level 0 by power iteration, B its smoother at T (SIPG
+// rows and general meshes have no closed-form Gershgorin bound here)
+static int level0_lambda(Ctx* c, const double* T, double* lam) {
   // a partition of a distributed unstructured mesh (collective): its owned rows,
   // the start vector's entries at their partition-major global indices, the
   // ghosts refreshed before every product, the norms all-reduced
@@ -91,19 +136,17 @@ int mg_dg_lambda(Ctx* c, const double* T, double* lam) {
   if (int e = gsum(nrm)) return e;
   for (double& v : h) v /= std::sqrt(nrm);
   HIPC(hipMemcpyAsync(c->mgx, h.data(), sizeof(double) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-  if (c->dggface) launch_dg_gface(c->dg, T, c->dggface, c->stream);
-  else if (!c->um) launch_dg_diag(c->dg, T, c->dinv, 1, c->stream);
+  const bool block = c->smoother0 != Smoother0::POINT;
+  if (c->smoother0 == Smoother0::DG_BLOCK) launch_dg_gface(c->dg, T, c->dggface, c->stream);  // as mg_prepare does
   std::vector<double> prt(1024);
   double l = 0.0;
-  if (c->aux_on) aux_refresh(c, T);  // the auxiliary-space level 0: the cell blocks of J(T)
-  else if (c->um) op_diag(c, T, c->dinv, 1);  // the algebraic multigrid's level 0: point Jacobi of J(T)
+  level0_setup(c, T);
   for (int it = 0; it < 30; ++it) {
     if (part)
       if (int e = halo(c, c->mgx)) return e;
     op_japply(c, T, c->mgx, c->w, nullptr, nullptr);
-    if (c->dggface) launch_dg_bsmooth(c->dg, nullptr, c->w, nullptr, c->dggface, 1.0, c->w, 0, c->stream);  // in place, per cell
-    if (c->aux_on) aux_smooth(c, nullptr, c->w, 1.0, c->w);  // B^-1 where dinv is applied (in place, per cell)
-    const int nb = launch_mg_pow(n, (c->dggface || c->aux_on) ? nullptr : c->dinv, c->w, c->partials, c->stream);
+    if (block) level0_smooth(c, nullptr, c->w, 1.0, c->w, 0, n);  // B^-1 in place, per cell; POINT: dinv below
+    const int nb = launch_mg_pow(n, block ? nullptr : c->dinv, c->w, c->partials, c->stream);
     HIPC(hipMemcpyAsync(prt.data(), c->partials, sizeof(double) * (size_t)nb, hipMemcpyDeviceToHost, c->stream));
     HIPC(hipStreamSynchronize(c->stream));
     double s2 = 0.0;
@@ -117,15 +160,16 @@ int mg_dg_lambda(Ctx* c, const double* T, double* lam) {
   return TV_OK;
 }
 
-// The DG level-0 smoother weight omega0 = 2 / (1.21 lambda_max) is estimated
-// lazily, at the first multigrid solve (or V-cycle application), from the
-// temperature it will precondition -- the Robin term 4 a_rad T^3 of the cell
-// blocks vanishes at the T = 0 a freshly created context holds
-int mg_dg_weight(Ctx* c, const double* T) {
-  if (!(c->mg_dg || c->amg_on) || c->mg_omega0 > 0.0) return TV_OK;
+// Level 0's smoother weight where no bound is known in advance (the DG1 cell
+// blocks, the algebraic hierarchies): estimated lazily, at the first multigrid
+// solve (or V-cycle application), from the temperature it will precondition
+// -- the Robin term 4 a_rad T^3 vanishes at the T = 0 a freshly created context
+// holds.  omega0 = 2 / (1.21 lambda_max) before the multiplicative box cycle,
+// the coarse levels' 2 / (1.1 lambda_max) for the additive level 0 of AMG
+int level0_weight(Ctx* c, const double* T) {
+  if (!(c->smoother0 == Smoother0::DG_BLOCK || c->amg_on) || c->mg_omega0 > 0.0) return TV_OK;
   double lam = 0.0;
-  if (int e = mg_dg_lambda(c, T, &lam)) return e;
-  // AMG level 0 (additive point Jacobi): the coarse levels' 2 / (1.1 lambda)
+  if (int e = level0_lambda(c, T, &lam)) return e;
   c->mg_omega0 = c->amg_on ? 2.0 / (1.1 * lam) : 2.0 / (1.1 * 1.1 * lam);
   return TV_OK;
 }
@@ -339,9 +383,9 @@ int mg_setup(Ctx* c) {
   HIPC(hipMemsetAsync(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
   if (dg) {
     // level 1: the CG1 space of the same box (two-level DG -> CG, then the CG hierarchy)
-    c->mg_dg = true;
+    c->smoother0 = Smoother0::DG_BLOCK;
     HIPC(tv_dev_alloc(&c->dggface, sizeof(double) * (size_t)dg_gface_size(c->dg), kMemDoubles));
-    c->mg_omega0 = 0.0;  // estimated at the first solve, at its T (mg_dg_weight)
+    c->mg_omega0 = 0.0;  // estimated at the first solve, at its T (level0_weight)
     if (int e = mg_add_cg_level(c, Xf, da)) return e;
   } else {
     c->mg_omega0 = mg_omega(mg_gershgorin(Xf, da));
@@ -354,13 +398,8 @@ int mg_setup(Ctx* c) {
     std::vector<char> is_c[3];  // fine node kept on this level
     int coarse[3];
     if (!mg_next_level(Xp, da, automatic, Xc, is_c, coarse)) break;
-    c->mg.emplace_back();
+    if (int e = mg_add_cg_level(c, Xc, da)) return e;
     MgLevel& L = c->mg.back();
-    for (int s = 0; s < 3; ++s) L.X[s] = Xc[s];
-    if (int e = build_cg_grid(c, 3, L.X, 0, (int)L.X[2].size(), 0, 0, true, true, L.g, L.coef, &L.bnodes, L.ffbuf))
-      return e;
-    if (int e = mg_level_vectors(c, L)) return e;
-    L.omega = mg_omega(mg_gershgorin(L.X, da));
     // transfer maps (finer level Xp -> this level)
     MgXfer& x = L.xf;
     std::vector<int> ri[3];
@@ -394,13 +433,15 @@ int mg_setup(Ctx* c) {
 }
 
 // per Newton iteration: T injected down the hierarchy (DG: the vertex mean of
-// the cell-local values onto the CG level), coarse Jacobi diagonals
-
+// the cell-local values onto the CG level, and the facet means of level 0's
+// cell blocks), coarse Jacobi diagonals
 int mg_prepare(Ctx* c, const double* T) {
   if (c->amg_on) return TV_OK;  // the algebraic hierarchy is T-independent (tv_amg.cpp)
-  // a DG1 slab: level 1's T = the vertex means on its owned vertex planes,
-  // summed over the slabs into the replicated vector (each plane from one slab)
-  const bool dgpart = c->mg_dg && c->n_parts > 1;
+  const bool dg = c->smoother0 == Smoother0::DG_BLOCK;
+  if (c->n_parts > 1 && !dg) return mg_prepare_dist(c, T);  // slabs of a CG1 box (tv_mgdist.cpp)
+  // a DG1 slab: level 1 onwards is replicated (mg_setup); its T = the vertex
+  // means on the slab's owned vertex planes, summed over the slabs (each plane from one slab)
+  const bool dgpart = dg && c->n_parts > 1;
   auto dg_T = [&](MgLevel& L) -> int {
     if (!dgpart) {
       launch_mg_dg_T(c->dg, T, L.T, 0, c->stream);
@@ -412,7 +453,7 @@ int mg_prepare(Ctx* c, const double* T) {
   };
   // after the first call (dinv interiors in place): the CG levels below the
   // base in two launches (launch_mg_prepare)
-  const size_t base = c->mg_dg ? 1 : 0;  // DG: level 1 is the vertex mean of the DG field
+  const size_t base = dg ? 1 : 0;  // DG: level 1 is the vertex mean of the DG field
   const size_t ncg = c->mg.size() - std::min(c->mg.size(), base);
   bool ready = ncg > 0 && ncg <= (size_t)kMgPrepMax;
   for (size_t l = base; l < c->mg.size() && ready; ++l)
@@ -421,7 +462,7 @@ int mg_prepare(Ctx* c, const double* T) {
     if (base == 1) {
       MgLevel& L = c->mg[0];
       if (int e = dg_T(L)) return e;
-      if (c->dggface) launch_dg_gface(c->dg, T, c->dggface, c->stream);
+      launch_dg_gface(c->dg, T, c->dggface, c->stream);
       launch_cg_diag(L.g, L.T, L.dinv, 1, c->stream, true);
     }
     MgPrep p{};
@@ -442,11 +483,10 @@ int mg_prepare(Ctx* c, const double* T) {
   const double* Tf = T;
   for (size_t l = 0; l < c->mg.size(); ++l) {
     MgLevel& L = c->mg[l];
-    if (l == 0 && c->mg_dg) {
+    if (l == 0 && dg) {
       if (int e = dg_T(L)) return e;
-      if (c->dggface) launch_dg_gface(c->dg, T, c->dggface, c->stream);
-    }
-    else launch_mg_inject(L.xf, Tf, L.T, c->stream);
+      launch_dg_gface(c->dg, T, c->dggface, c->stream);
+    } else launch_mg_inject(L.xf, Tf, L.T, c->stream);
     launch_cg_diag(L.g, L.T, L.dinv, 1, c->stream, L.dinv_interior);
     L.dinv_interior = true;
     Tf = L.T;
@@ -454,12 +494,6 @@ int mg_prepare(Ctx* c, const double* T) {
   return TV_OK;
 }
 
-// V-cycle on coarse level l >= 1 (index l - 1 in c->mg): rhs b -> x; the
-// pre-smoothing step from 0 (x = omega D^-1 b) was formed by the restriction
-// that produced b.  The J x before the restriction is complete (k_cg_addfaces:
-// a per-node facet term inside the 27-point gather measured slower); the one
-// before the post-smoothing leaves the facet terms of the faces along the
-// march to that pointwise consumer (FaceAdd).
 // The prolongation from coarse level index ci (c->mg[ci]) into its finer level:
 // where that level has a post-smoothing step (not the coarsest) and the
 // 2 x 2 block prolongation runs, the step is applied on the fly (CoarsePost)
@@ -477,6 +511,12 @@ void mg_prolong_from(Ctx* c, size_t ci, double* xf, const double* mask) {
 
 static const char kRRChunkMsg[] = "GMG: fused residual restriction refused (march chunk out of range)";
 
+// V-cycle on coarse level l >= 1 (index l - 1 in c->mg): rhs b -> x; the
+// pre-smoothing step from 0 (x = omega D^-1 b) was formed by the restriction
+// that produced b.  The J x before the restriction is complete (k_cg_addfaces:
+// a per-node facet term inside the 27-point gather measured slower); the one
+// before the post-smoothing leaves the facet terms of the faces along the
+// march to that pointwise consumer (FaceAdd).
 int mg_level(Ctx* c, size_t l) {
   MgLevel& L = c->mg[l - 1];
   hipStream_t s = c->stream;
@@ -504,37 +544,36 @@ int mg_level(Ctx* c, size_t l) {
   return TV_OK;
 }
 
-// level 0: x0 = omega dinv r is in c->mgx (k_mg_update); coarse correction,
-// post-smoothing into z with the (z.z, z.r) reduction tail
-int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
-  if (c->amg_on) return amg_apply0(c, tail);
+// the box cycle of one partition (and of a DG1 slab): x0 = omega0 B^-1 r is in
+// c->mgx (level0_update); coarse correction, post-smoothing into z with the
+// (z.z, z.r) reduction tail
+static int mg_cycle_box(Ctx* c, const double* T, const RedTail* tail) {
   const int64_t n = c->nT;
   hipStream_t s = c->stream;
   const double* mask = c->dir_on ? c->dinv : nullptr;  // Dirichlet: the free subspace
-  if (c->mg_dg) {  // DG1 level 0: complete DG J x (Robin facets inline), vertex sums / injection to CG1
+  // DG1 level 0: complete DG J x (Robin facets inline), vertex sums / injection to CG1
+  if (c->smoother0 == Smoother0::DG_BLOCK) {
     const DgGrid& d = c->dg;
     MgLevel& C = c->mg[0];
     if (c->n_parts > 1) {  // a slab (mg_setup): the replicated level 1, see there
       const int kg0 = c->plane_begin - d.k_begin;
-      if (int e = halo(c, c->mgx)) return -e;  // x0 of the ghost layers (J x0, the prolongation into them)
+      if (int e = halo(c, c->mgx)) return e;  // x0 of the ghost layers (J x0, the prolongation into them)
       launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
-      if (hipMemsetAsync(C.b, 0, sizeof(double) * (size_t)C.n, s) != hipSuccess)
-        return -c->fail(TV_ERR_HIP, "GMG: level-1 memset");
+      HIPC(hipMemsetAsync(C.b, 0, sizeof(double) * (size_t)C.n, s));
       launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, nullptr, 0.0, nullptr, kg0, s);
-      if (int e = allreduce_vec(c, C.b, C.n)) return -e;
+      if (int e = allreduce_vec(c, C.b, C.n)) return e;
       launch_mg_jacobi(C.n, c->st, C.b, nullptr, nullptr, C.dinv, C.omega, C.x, 0, s);  // pre-smoothing from 0
-      if (int e = mg_level(c, 1)) return -e;
+      if (int e = mg_level(c, 1)) return e;
       launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, kg0, s);
     } else {
       launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
       launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, C.dinv, C.omega, C.x, 0, s);
-      if (int e = mg_level(c, 1)) return -e;
+      if (int e = mg_level(c, 1)) return e;
       launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, 0, s);
     }
     launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
-    if (c->dggface)
-      return launch_dg_bpost(d, c->st, c->mgx, c->r, c->w, c->dggface, c->mg_omega0, c->z, c->partials, tail, s);
-    return launch_mg_post(n, c->st, c->mgx, c->r, c->w, nullptr, c->dinv, c->mg_omega0, c->z, c->partials, tail, s);
+    launch_dg_bpost(d, c->st, c->mgx, c->r, c->w, c->dggface, c->mg_omega0, c->z, c->partials, tail, s);
+    return TV_OK;
   }
   const FaceAdd fa = cg_face_add(c->cg, 0);
   if (!c->mg.empty()) {
@@ -547,7 +586,7 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
       // then the fused residual restriction (RRArgs) with level 1's pre-smoothing
       launch_cg_facet_faces(c->cg, T, c->mgx, c->st, s);
       if (!launch_mg_rrestrict(C.rr, c->st, c->r, c->mgx, cg_face_add_all(c->cg), C.b, C.dinv, C.omega, C.x, s))
-        return -c->fail(TV_ERR_STATE, kRRChunkMsg);
+        return c->fail(TV_ERR_STATE, kRRChunkMsg);
     } else if (fa.on && mg_restrict_folds_faces(C.xf) && n < kMgFoldFacesNodes) {
       launch_cg_japply_partial(c->cg, T, c->mgx, c->w, c->st, s);
       launch_mg_restrict(C.xf, c->st, c->r, c->w, &fa, mask, C.b, C.dinv, C.omega, C.x, s);
@@ -555,38 +594,42 @@ int mg_apply0(Ctx* c, const double* T, const RedTail* tail) {
       launch_cg_japply(c->cg, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
       launch_mg_restrict(C.xf, c->st, c->r, c->w, nullptr, mask, C.b, C.dinv, C.omega, C.x, s);
     }
-    if (int e = mg_level(c, 1)) return -e;
+    if (int e = mg_level(c, 1)) return e;
     mg_prolong_from(c, 0, c->mgx, mask);
   }
   // J x, post-smoothing and (z.z, z.r) in the march epilogue (+ the side-face pass)
-  {
-    const int nrec = launch_cg_japply_post(c->cg, T, c->mgx, c->r, c->dinv, c->mg_omega0, c->z, c->st, c->partials,
-                                           tail, s);
-    if (nrec >= 0) return nrec;
-  }
+  if (launch_cg_japply_post(c->cg, T, c->mgx, c->r, c->dinv, c->mg_omega0, c->z, c->st, c->partials, tail, s) >= 0)
+    return TV_OK;
   launch_cg_japply_partial(c->cg, T, c->mgx, c->w, c->st, s);
-  return launch_mg_post(n, c->st, c->mgx, c->r, c->w, &fa, c->dinv, c->mg_omega0, c->z, c->partials, tail, s);
+  launch_mg_post(n, c->st, c->mgx, c->r, c->w, &fa, c->dinv, c->mg_omega0, c->z, c->partials, tail, s);
+  return TV_OK;
 }
 
-int mg_iteration(Ctx* c, const double* T, int it) {
-  const int64_t n = c->nT;
+int mg_cycle(Ctx* c, const double* T, const RedTail* tail) {
+  if (c->amg_on) return amg_apply0(c, tail);  // the algebraic cycle, agglomerated on partitions (tv_amg.cpp)
+  if (c->n_parts > 1 && c->smoother0 != Smoother0::DG_BLOCK) return mg_cycle_dist(c, T, tail);
+  return mg_cycle_box(c, T, tail);
+}
+
+int mg_dist_begin(Ctx* c, const double* T) {
+  // the algebraic hierarchy is T-independent: level 0's weight at the first solve instead
+  if (int e = c->amg_on ? level0_weight(c, T) : mg_prepare(c, T)) return e;
+  if (c->dir_on)  // the prolongation masks level 0's ghost planes with dinv too
+    if (int e = halo(c, c->dinv)) return e;
+  if (c->mg_mask0)  // level 0's restriction mask: owned nodes, Dirichlet rows out
+    launch_mg_ownmask(c->nT, c->ownT_off, c->ownT_off + c->ownT_n, c->dir_on ? c->dinv : nullptr, c->mg_mask0,
+                      c->stream);
+  return TV_OK;
+}
+
+static int mg_iteration(Ctx* c, const double* T, int it) {
   RedTail t1{c->counters, c->partials, c->sums, c->st, 2, iter_stamp(c, it)};
   int np = 0;
   if (!op_japply_fused(c, T, &np, &t1, it))  // p <- z + b p ; w <- J p ; p.w ; alpha
     if (int e = reduce_logic(c, np, 1, 2, 1)) return e;
-  const FaceAdd fa = (c->mg_dg || c->um) ? FaceAdd{} : cg_face_add(c->cg, 0);  // DG, unstructured: w is complete
-  if (c->dggface)
-    launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it, 0,
-                      c->stream);
-  else if (c->aux_on)
-    launch_umdg_aux_update(c->udg, c->aux, c->st, c->pA, c->pB, c->w, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it,
-                           0, c->stream);
-  else
-    launch_mg_update(n, c->st, c->pA, c->pB, c->w, &fa, c->dinv, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, it, 0,
-                     c->stream);
+  level0_update(c, it, false, 0, c->nT);
   RedTail t2{c->counters + kTailCounters, c->partials, c->sums, c->st, 3, nullptr};
-  const int nrec = mg_apply0(c, T, &t2);  // z <- V(r); z.z, z.r; beta, convergence
-  return nrec < 0 ? -nrec : TV_OK;
+  return mg_cycle(c, T, &t2);  // z <- V(r); z.z, z.r; beta, convergence
 }
 
 // The three multigrid solves queue alike.  An MG iteration is ~25 launches: the
@@ -614,18 +657,10 @@ int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
   const int64_t n = c->nT;
   solve_begin(c, c->solve_gate);
   if (int e = mg_prepare(c, T)) return e;
-  if (int e = mg_dg_weight(c, T)) return e;
-  if (c->dggface)
-    launch_dg_bupdate(c->dg, c->st, c->pA, c->pB, c->w, c->dggface, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0, 1,
-                      c->stream);  // dx <- 0, x0 <- omega B^-1 r
-  else if (c->aux_on)
-    launch_umdg_aux_update(c->udg, c->aux, c->st, c->pA, c->pB, c->w, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0,
-                           1, c->stream);  // x0 <- omega B^-1 r (cell blocks)
-  else
-    launch_mg_update(n, c->st, c->pA, c->pB, c->w, nullptr, c->dinv, c->mg_omega0, c->r, c->f[TV_F_DX].ptr, c->mgx, 0, 1,
-                     c->stream);  // dx <- 0, x0 <- omega dinv r
+  if (int e = level0_weight(c, T)) return e;
+  level0_update(c, 0, true, 0, n);  // dx <- 0, x0 <- omega0 B^-1 r
   RedTail t0{c->counters + kTailCounters, c->partials, c->sums, c->st, 1, nullptr};
-  if (const int nrec = mg_apply0(c, T, &t0); nrec < 0) return -nrec;  // z <- V(r); dp, beta (KSPCG init)
+  if (int e = mg_cycle(c, T, &t0)) return e;  // z <- V(r); dp, beta (KSPCG init)
   auto iterate = [&](int it, int, int) { return mg_iteration(c, T, it); };
   auto published = [&]() -> int {
     if (!post) return TV_OK;
@@ -634,8 +669,8 @@ int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
     return queue_newton_norm(c, c->sums);
   };
   if (int e = krylov_drive(c, mg_krylov_policy(c), iterate, published, its, reason)) return e;
-  // level 0 updates dx in pairs of iterations from iteration 1 on (k_mg_update /
-  // k_dg_bupdate DXU): solves of 0 / 1 iterations and the last step of an odd-length one
+  // level 0 updates dx in pairs of iterations from iteration 1 on (level0_update's
+  // kernels, DXU): solves of 0 / 1 iterations and the last step of an odd-length one
   if (!post) launch_mg_dx_finish(n, c->st, c->pA, c->pB, c->f[TV_F_DX].ptr, *its, c->stream);
   return TV_OK;
 }
@@ -644,86 +679,45 @@ int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post) {
 
 using namespace tv;
 
-// tv_precond_apply on a partition (collective: every rank calls it): the
-// operator the partitioned Krylov solve applies, on this rank's owned dofs --
-// Jacobi, or the partitioned V-cycle (GLOBAL: the distributed cycle of the
-// whole box; LOCAL: this slab's own cycle)
-static int precond_apply_part(Ctx* c, const double* r_dev, double* z_dev) {
-  if (int e = require_comm(c, "tv_precond_apply")) return e;
-  if (c->um || c->fam_T != TV_CG) return c->fail(TV_ERR_ARG, "tv_precond_apply: partitioned CG1 box meshes");
-  const double* T = c->f[TV_F_T].ptr;
-  const int64_t off = c->ownT_off, n = c->ownT_n;
-  hipStream_t s = c->stream;
-  if (int e = halo(c, c->f[TV_F_T].ptr)) return e;  // the PC setup reads the ghost planes' T (side-face facets)
-  launch_cg_diag(c->cg, T, c->dinv, 1, s, c->dinv_interior);
-  c->dinv_interior = true;
-  if (c->dir_on) launch_bc_mask(c, c->dinv);
-  if (!c->mg_on) {
-    launch_mg_jacobi(n, nullptr, r_dev, nullptr, nullptr, c->dinv + off, 1.0, z_dev, 0, s);
-  } else {
-    PcgState h{};
-    HIPC(hipMemcpyAsync(c->st, &h, sizeof(PcgState), hipMemcpyHostToDevice, s));
-    if (int e = mg_prepare_dist(c, T)) return e;
-    if (c->dir_on)
-      if (int e = halo(c, c->dinv)) return e;
-    if (c->mg_mask0) launch_mg_ownmask(c->nT, off, off + n, c->dir_on ? c->dinv : nullptr, c->mg_mask0, s);
-    HIPC(hipMemcpyAsync(c->r + off, r_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    int64_t woff, nwin;  // deep ghosts: r on the ghost planes, x0 on the write window
-    fine_window(c, &woff, &nwin);
-    if (c->ghost_depth > 1)
-      if (int e = halo(c, c->r)) return e;
-    launch_mg_jacobi(nwin, c->st, c->r + woff, nullptr, nullptr, c->dinv + woff, c->mg_omega0, c->mgx + woff, 0, s);
-    if (int e = mg_apply0_dist(c, T, nullptr)) return e;
-    HIPC(hipMemcpyAsync(z_dev, c->z + off, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
-  }
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(s));
-  return TV_OK;
-}
-
 extern "C" {
 
+// On a partition (collective: every rank calls it): the operator the partitioned
+// Krylov solve applies, on this rank's owned dofs -- Jacobi, or the partitioned
+// V-cycle (GLOBAL: the distributed cycle of the whole box; LOCAL: this slab's own)
 int tv_precond_apply(void* ctx, const double* r_dev, double* z_dev) {
   Ctx* c = static_cast<Ctx*>(ctx);
   if (!c || !r_dev || !z_dev) return TV_ERR_ARG;
   hipSetDevice(c->device);
   HIPC(hipDeviceSynchronize());  // inputs written on other streams (header)
-  if (c->n_parts > 1) return precond_apply_part(c, r_dev, z_dev);
+  const bool part = c->n_parts > 1;
   const double* T = c->f[TV_F_T].ptr;
-  const int64_t n = c->nT;
-  hipStream_t s = c->stream;
-  // the PC setup of the Newton iteration at this T
-  if (c->aux_on) {
-    aux_refresh(c, T);  // the cell blocks that follow T
-  } else if (!c->dggface) {
-    if (!c->um && c->fam_T == TV_CG) {
-      launch_cg_diag(c->cg, T, c->dinv, 1, s, c->dinv_interior);
-      c->dinv_interior = true;
-    } else {
-      op_diag(c, T, c->dinv, 1);
-    }
+  if (part) {
+    if (int e = require_comm(c, "tv_precond_apply")) return e;
+    if (c->um || c->fam_T != TV_CG) return c->fail(TV_ERR_ARG, "tv_precond_apply: partitioned CG1 box meshes");
+    if (int e = halo(c, c->f[TV_F_T].ptr)) return e;  // the PC setup reads the ghost planes' T (side-face facets)
   }
+  const int64_t off = c->ownT_off, n = c->ownT_n;  // one partition: every dof
+  hipStream_t s = c->stream;
+  level0_setup(c, T);  // the PC setup of the Newton iteration at this T
   // Dirichlet mode: the solve's preconditioner acts on the free subspace only
   // (dinv = 0 on the constrained rows, as k_bc_lift sets it before every solve;
   // the V-cycle masks its transfers with the same dinv)
   if (c->dir_on && c->fam_T == TV_CG) launch_bc_mask(c, c->dinv);
-  if (c->mg_dg || c->amg_on)
-    if (int e = mg_dg_weight(c, T)) return e;
+  if (int e = level0_weight(c, T)) return e;
   if (!c->mg_on) {
-    launch_mg_jacobi(n, nullptr, r_dev, nullptr, nullptr, c->dinv, 1.0, z_dev, 0, s);  // z = dinv .* r
+    launch_mg_jacobi(n, nullptr, r_dev, nullptr, nullptr, c->dinv + off, 1.0, z_dev, 0, s);  // z = dinv .* r
   } else {
     PcgState h{};  // running state: the V-cycle's kernels skip work once a solve is done
     HIPC(hipMemcpyAsync(c->st, &h, sizeof(PcgState), hipMemcpyHostToDevice, s));
-    if (int e = mg_prepare(c, T)) return e;
-    HIPC(hipMemcpyAsync(c->r, r_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
-    if (c->dggface)  // x0 = omega0 B^-1 r (cell blocks)
-      launch_dg_bsmooth(c->dg, c->st, c->r, nullptr, c->dggface, c->mg_omega0, c->mgx, 0, s);
-    else if (c->aux_on)
-      aux_smooth(c, c->st, c->r, c->mg_omega0, c->mgx);
-    else
-      launch_mg_jacobi(n, c->st, c->r, nullptr, nullptr, c->dinv, c->mg_omega0, c->mgx, 0, s);
-    if (const int nrec = mg_apply0(c, T, nullptr); nrec < 0) return -nrec;
-    HIPC(hipMemcpyAsync(z_dev, c->z, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    if (int e = part ? mg_dist_begin(c, T) : mg_prepare(c, T)) return e;
+    HIPC(hipMemcpyAsync(c->r + off, r_dev, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    int64_t woff, nwin;  // deep-ghost slabs: r on the ghost planes, x0 on the write window
+    fine_window(c, &woff, &nwin);
+    if (c->ghost_depth > 1)
+      if (int e = halo(c, c->r)) return e;
+    level0_smooth(c, c->st, c->r, c->mg_omega0, c->mgx, woff, nwin);  // x0 = omega0 B^-1 r
+    if (int e = mg_cycle(c, T, nullptr)) return e;
+    HIPC(hipMemcpyAsync(z_dev, c->z + off, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
   }
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(s));

@@ -481,18 +481,8 @@ int newton(Ctx* c, int* out_its, int* out_kits, int* out_conv, int step_end, boo
   int q = 0;          // Newton iterations queued
   int pending = -1;   // a queued iteration whose test the host has not read yet
   for (;;) {
-    if (c->aux_on) {  // auxiliary-space level 0: the blocks of the cells with an exterior facet follow u
-      aux_refresh(c, T);
-    } else if (!c->dggface) {  // J(u) (matrix-free) + Jacobi PC setup (DG GMG: cell blocks)
-      if (!c->um && c->fam_T == TV_CG) {
-        // the T-independent interior of dinv is written once; then the boundary nodes only
-        if (!dinv_fresh) launch_cg_diag(c->cg, T, c->dinv, 1, c->stream, c->dinv_interior);
-        c->dinv_interior = true;
-      } else {
-        op_diag(c, T, c->dinv, 1);
-        if (c->um && !c->um_dg) launch_um_robin_fold(c->umg, T, c->stream);  // J(u) of the solve (structured topology)
-      }
-    }
+    level0_setup(c, T, dinv_fresh);  // the preconditioner's B at u
+    if (c->um && !c->um_dg) launch_um_robin_fold(c->umg, T, c->stream);  // J(u) of the solve (structured topology)
     dinv_fresh = false;
     const bool dir = c->dir_on && c->fam_T == TV_CG;
     if (dir)

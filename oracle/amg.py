@@ -19,7 +19,7 @@ Algorithm (each step as tv_amg.cpp states it):
     R = P^T; A_c = R (A P) in double;
   * coarse weights omega_l = 2 / (1.1 lambda_max(D^-1 A_l)) (20 Lanczos steps);
     level-0 weight 2 / (1.1 lambda_max(D^-1 J(T))) (30 iterations, the
-    device's mg_dg_lambda);
+    device's level0_lambda);
   * structured topology (build(V, dims=(N0, N1, N2)), vertex i + N0 (j + N1 k)):
     P = the geometric prolongation of the index space instead (tv_amg.cpp
     geometric_p: every other vertex kept per axis plus the last when the cell
@@ -95,7 +95,7 @@ def lam_max_host(A, dinv, its):
 
 
 def lam_max_device(J, dinv, its=30):
-    """tv_mgsolve.cpp mg_dg_lambda: x = h / |h|, then w = D^-1 J x, l = |w|, x = w / l."""
+    """tv_mgsolve.cpp level0_lambda: x = h / |h|, then w = D^-1 J x, l = |w|, x = w / l."""
     x = _xorshift_start(J.shape[0], 0x9E3779B97F4A7C15)
     x = x / np.sqrt(np.dot(x, x))
     lam = 0.0

@@ -35,7 +35,7 @@ GROUPS = {
     "mg_restrict": ("k_mg_restrict_pairs",),
     "mg_prolong": ("k_mg_prolong_blk",),
 }
-# one V-cycle (tv_mgsolve.cpp mg_apply0): every launch of these, all levels, per
+# one V-cycle (tv_mgsolve.cpp mg_cycle): every launch of these, all levels, per
 # k_mg_post_faces dispatch (one per V-cycle)
 VCYCLE = ("k_cg_march<1, false", "k_cg_addfaces", "k_mg_restrict", "k_mg_rrestrict", "k_cg_faces_all", "k_mg_prolong",
           "k_mg_jacobi", "k_mg_post_faces")
