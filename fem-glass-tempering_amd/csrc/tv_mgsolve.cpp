@@ -544,13 +544,20 @@ int mg_level(Ctx* c, size_t l) {
   return TV_OK;
 }
 
+// Dirichlet mode constrains a CG1 temperature only (a DG1 dof belongs to no
+// facet: tv_set_dirichlet).  The masks of the cycle's transfers are dinv with
+// its constrained rows zeroed (launch_bc_mask), which nothing writes on a DG1
+// context: there dinv stays all zero, and a cycle masked with it would keep
+// only its block smoothing (z = omega0 B^-1 r)
+static bool dirichlet_masks(const Ctx* c) { return c->dir_on && c->fam_T == TV_CG; }
+
 // the box cycle of one partition (and of a DG1 slab): x0 = omega0 B^-1 r is in
 // c->mgx (level0_update); coarse correction, post-smoothing into z with the
 // (z.z, z.r) reduction tail
 static int mg_cycle_box(Ctx* c, const double* T, const RedTail* tail) {
   const int64_t n = c->nT;
   hipStream_t s = c->stream;
-  const double* mask = c->dir_on ? c->dinv : nullptr;  // Dirichlet: the free subspace
+  const double* mask = dirichlet_masks(c) ? c->dinv : nullptr;  // Dirichlet: the free subspace
   // DG1 level 0: complete DG J x (Robin facets inline), vertex sums / injection to CG1
   if (c->smoother0 == Smoother0::DG_BLOCK) {
     const DgGrid& d = c->dg;
@@ -614,11 +621,11 @@ int mg_cycle(Ctx* c, const double* T, const RedTail* tail) {
 int mg_dist_begin(Ctx* c, const double* T) {
   // the algebraic hierarchy is T-independent: level 0's weight at the first solve instead
   if (int e = c->amg_on ? level0_weight(c, T) : mg_prepare(c, T)) return e;
-  if (c->dir_on)  // the prolongation masks level 0's ghost planes with dinv too
+  if (dirichlet_masks(c))  // the prolongation masks level 0's ghost planes with dinv too
     if (int e = halo(c, c->dinv)) return e;
   if (c->mg_mask0)  // level 0's restriction mask: owned nodes, Dirichlet rows out
-    launch_mg_ownmask(c->nT, c->ownT_off, c->ownT_off + c->ownT_n, c->dir_on ? c->dinv : nullptr, c->mg_mask0,
-                      c->stream);
+    launch_mg_ownmask(c->nT, c->ownT_off, c->ownT_off + c->ownT_n, dirichlet_masks(c) ? c->dinv : nullptr,
+                      c->mg_mask0, c->stream);
   return TV_OK;
 }
 

@@ -403,7 +403,10 @@ int tv_set_initial_condition(void* ctx, double T0);
  * it -- its own code cannot run (:241 self.fs, :180 material_model.T_ambient,
  * and the bc never reaches NonlinearProblem at :331).  Only with model_mode =
  * TV_MODEL_PAPER (TV_ERR_STATE otherwise).  DG temperature: no dof belongs to
- * a facet, so the constraint is empty (as locate_dofs_topological would find). */
+ * a facet, so the constraint is empty (as locate_dofs_topological would find):
+ * the call is accepted and changes nothing, neither the solve nor its
+ * preconditioner (the multigrid masks its transfers for a CG1 temperature
+ * only; tests/test_multigrid_dg.py holds the results bitwise equal). */
 int tv_set_dirichlet(void* ctx, int enable, double value);
 /* Relaxation factor of the stress update of a single-problem context (box,
  * unstructured, slab part, unstructured part).  TAYLOR (the default) is the

@@ -7,7 +7,7 @@ What it restates, step by step (fem-glass-tempering_amd/csrc):
   * tv_umdg_aux.hip k_umdg_binv: B_e = the diagonal NL x NL block of J(T) of cell e,
     Robin Jacobian of its exterior facets included -- here the diagonal blocks of
     the oracle's assembled DG `HeatForm.jacobian(T)`, inverted by numpy;
-  * tv_mgsolve.cpp mg_dg_lambda / mg_dg_weight with B^-1 in the place of dinv:
+  * tv_mgsolve.cpp level0_lambda / level0_weight with B^-1 in the place of dinv:
     omega0 = 2 / (1.1 lambda), lambda = |B^-1 J x| after 30 power iterations from
     the xorshift start vector indexed by DEVICE dof l nc + e;
   * tv_amg.cpp aux_setup: level 1 = the CG1 cell operator V = M + dt alpha K of
@@ -77,6 +77,21 @@ def diagonal_blocks(J, nl):
     return B
 
 
+def power_lambda(J, smooth, dim, its=30):
+    """tv_mgsolve.cpp level0_lambda: |B^-1 J x| after `its` power iterations (not
+    converged: the start vector is part of the result) from the xorshift start
+    vector, which the device indexes by ITS dof l n_cells + cell; J and `smooth`
+    (r -> B^-1 r) cell-major.  Shared with tests/dg_gmg_reference.py."""
+    x = host_layout(dim, OA._xorshift_start(J.shape[0], 0x9E3779B97F4A7C15))  # started in device dof order
+    x = x / np.sqrt(np.dot(x, x))
+    lam = 0.0
+    for _ in range(its):
+        w = smooth(J @ x)
+        lam = np.sqrt(np.dot(w, w))
+        x = w / lam
+    return lam
+
+
 class AuxCycle:
     """The TV_PC_AUX preconditioner at temperature T (cell-major) on mesh `name`."""
 
@@ -100,15 +115,7 @@ class AuxCycle:
         return np.einsum("eij,ej->ei", self.Binv, r.reshape(-1, self.nl)).reshape(-1)
 
     def _lambda(self, its=30):
-        n = self.J.shape[0]
-        x = host_layout(self.dim, OA._xorshift_start(n, 0x9E3779B97F4A7C15))  # started in device dof order
-        x = x / np.sqrt(np.dot(x, x))
-        lam = 0.0
-        for _ in range(its):
-            w = self.smooth(self.J @ x)
-            lam = np.sqrt(np.dot(w, w))
-            x = w / lam
-        return lam
+        return power_lambda(self.J, self.smooth, self.dim, its)
 
     @property
     def n_levels(self):

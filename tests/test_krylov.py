@@ -9,15 +9,17 @@ last_krylov_iterations is that solve's count, the field "dx" its result, and
 T_after == T_before - dx bitwise.  T and T_prev are set before every solve.
 
 Reference preconditioners: r / diag J (Jacobi forms; get_field returns the
-reference's dof order for DG too) and gmg_reference.vcycle_reference at the
-automatic depth (multigrid).  So the multigrid cases pin the cycle AS THE SOLVE
+reference's dof order for DG too), gmg_reference.vcycle_reference at the
+automatic depth (multigrid, CG1) and dg_gmg_reference.DgGmgCycle (multigrid,
+DG1: "gmg-dg").  So the multigrid cases pin the cycle AS THE SOLVE
 RUNS IT (mg_iteration: x0 = omega D^-1 r inside the PCG update launch, the
 kernels gated on the device state, the sums from the reduction tails), not the
 tv_precond_apply entry point.
 
 Tolerances (relative L2 of dx against the long-double iterate): 1e-12 for the
 Jacobi forms (the operator tolerance of test_gpu_parity: rounding only), 1e-11
-for multigrid (the tolerance at which the V-cycle itself is pinned).  The
+for multigrid (the tolerance at which the V-cycle itself is pinned; 1e-10 for
+the DG1 cycle, whose cell-block solve uses approximate reciprocals).  The
 float64 run of the same reference is printed beside each result: it is the
 rounding floor, <= 4e-16 on "plate" for all 27 Jacobi and all 5 multigrid
 iterates.  Everything else is exact: counts, bitwise equalities, error strings.
@@ -29,6 +31,7 @@ import sys
 import numpy as np
 import pytest
 
+import dg_gmg_reference as DGR
 from gmg_reference import auto_levels, vcycle_reference
 from krylov_reference import kspcg
 from oracle import tv_oracle as O
@@ -46,6 +49,14 @@ GRIDS = {
     # tests/test_gpu_parity.AXES
     "2d": [np.linspace(0.0, 3.0, 13), np.linspace(0.0, 1.0, 5)],
     "3d": [np.linspace(0.0, 2.0, 9), np.linspace(0.0, 2.0, 7), np.linspace(0.0, 1.0, 5)],
+    # the DG1 box multigrid.  "dg": dg_gmg_reference.GRIDS["two_blocks"] (315 cells: two workgroups of cells,
+    # the second partial).  "dg-graded": "graded" above at half its cell counts (8 x 8 x 3 cells; the
+    # neighbours' lengths in the SIPG penalty) -- the oracle takes half a minute to assemble DG1 on "graded"
+    # itself, and on dg_gmg_reference.GRIDS["graded"] the reference's dp_6 lies 5e-4 from the threshold
+    # (a marginal count, which end_reason_sequence refuses); here the nearest is 5e-2
+    "dg": DGR.GRIDS["two_blocks"],
+    "dg-graded": [np.concatenate([np.linspace(0.0, 0.5, 5), np.linspace(0.5, 2.5, 5)[1:]]),
+                  np.linspace(0.0, 2.0, 9), np.linspace(0.0, 0.75, 4)],
 }
 # id: (grid, family, mesh kind, reference B, constructor arguments, TVFEM_MG_RR, Krylov form the context must report)
 FORMS = {
@@ -59,8 +70,12 @@ FORMS = {
     "gmg-plate": ("plate", "CG", "box", "gmg", dict(preconditioner="gmg"), "0", "kspcg"),
     "gmg-plate-rr": ("plate", "CG", "box", "gmg", dict(preconditioner="gmg"), "1", "kspcg"),
     "gmg-graded": ("graded", "CG", "box", "gmg", dict(preconditioner="gmg"), "0", "kspcg"),
+    # DG1 temperature: cell-block smoothing (k_dg_bupdate's init, first, odd and even forms), the CG1 box below
+    "gmg-dg": ("dg", "DG", "box", "gmg-dg", dict(preconditioner="gmg"), None, "kspcg"),
+    "gmg-dg-graded": ("dg-graded", "DG", "box", "gmg-dg", dict(preconditioner="gmg"), None, "kspcg"),
 }
-TOL = {"jacobi": 1e-12, "gmg": 1e-11}
+# gmg-dg: the bar at which tests/test_multigrid_dg.py pins the DG cycle itself
+TOL = {"jacobi": 1e-12, "gmg": 1e-11, "gmg-dg": 1e-10}
 
 
 def _gpu():
@@ -106,6 +121,8 @@ def precond(grid, fam, pc):
     if pc == "jacobi":
         d = s["J"].diagonal()
         return lambda r: r / d
+    if pc == "gmg-dg":  # omega0 is estimated at the first solve's T: every solve here starts from s["T"]
+        return DGR.DgGmgCycle(DGR.DgBox(GRIDS[grid], DT), s["T"])
     mp = dict(O.MAIN_MODEL_PARAMS)
     return vcycle_reference(GRIDS[grid], s["T"], mp, DT, auto_levels(GRIDS[grid], DT, mp["alpha"]))
 

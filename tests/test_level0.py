@@ -5,8 +5,10 @@ linear solve against the device's own PCApply.
 In a solve x0 = omega0 B^-1 r comes from the init form of the update launch
 (level0_update), in tv_precond_apply from the smooth launch (level0_smooth);
 both then run the same cycle.  tests/test_krylov.py pins the in-solve path
-against a reference for the CG box only; the numpy restatements pin
-tv_precond_apply for the others.  This ties the two entry points together:
+against a reference for the CG and DG boxes; the numpy restatements pin
+tv_precond_apply for every case (cg-box: tests/gmg_reference.py, dg-box:
+tests/dg_gmg_reference.py, um-amg*: oracle/amg.py, umdg-aux:
+tests/dg_aux_reference.py).  This ties the two entry points together:
 with F = tv_residual(T), z = tv_precond_apply(F) and w = tv_jacobian_apply(z),
 the iterate after one KSPCG iteration is dx = alpha z, alpha = (F.z) / (z.w).
 

@@ -266,11 +266,14 @@ VCYCLE_CASES = {
     # do not apply
     "thin_x_4": ([np.linspace(0.0, 0.3, 4), np.linspace(0.0, 2.0, 17), np.linspace(0.0, 1.0, 9)], 4),
 }
+# a case of VCYCLE_CASES at (alpha, dt) off the defaults (1, 0.1): dt alpha in the cell operator and the
+# Gershgorin weights, dt alone on the Robin facet terms
+VCYCLE_PARAMS = {"odd_graded_4_alpha": ("odd_graded_4", 0.37, 0.25)}
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("fused", [False, True], ids=["jx_restrict", "fused_restrict"])
-@pytest.mark.parametrize("case", list(VCYCLE_CASES))
+@pytest.mark.parametrize("case", list(VCYCLE_CASES) + list(VCYCLE_PARAMS))
 def test_gmg_vcycle_operator_matches_numpy_restatement(case, fused, monkeypatch):
     """tv_precond_apply (one V-cycle: the PCApply of the solve) against the numpy
     V-cycle above at a non-uniform T, to 1e-11; the operator is symmetric (CG
@@ -282,10 +285,11 @@ def test_gmg_vcycle_operator_matches_numpy_restatement(case, fused, monkeypatch)
     monkeypatch.setenv("TVFEM_MG_RR", "1" if fused else "0")
     from tvfem import RectilinearMesh
     from tvfem.problem import ThermoViscoProblem
-    axes, levels = VCYCLE_CASES[case]
     mp = dict(O.MAIN_MODEL_PARAMS)
+    grid, mp["alpha"], dt = VCYCLE_PARAMS.get(case, (case, mp["alpha"], 0.1))
+    axes, levels = VCYCLE_CASES[grid]
     cfg = {"T": CG, "sigma": CG}
-    p = ThermoViscoProblem(RectilinearMesh(axes), (0.0, 1.0), 0.1, cfg, mp, verbose=False, part_axis=2,
+    p = ThermoViscoProblem(RectilinearMesh(axes), (0.0, 1.0), dt, cfg, mp, verbose=False, part_axis=2,
                            preconditioner="gmg", mg_levels=levels)
     p.setup()
     n = p.get_field("T").size
@@ -295,7 +299,7 @@ def test_gmg_vcycle_operator_matches_numpy_restatement(case, fused, monkeypatch)
     p._flush()
     nlev = levels
     if nlev == 0:  # the automatic depth of mg_setup
-        da, nlev, Xp = 0.1 * mp["alpha"], 1, [np.asarray(a) for a in axes]
+        da, nlev, Xp = dt * mp["alpha"], 1, [np.asarray(a) for a in axes]
         while True:
             cells = [len(a) - 1 for a in Xp]
             h = min((a[-1] - a[0]) / c for a, c in zip(Xp, cells) if c >= 1)
@@ -304,7 +308,7 @@ def test_gmg_vcycle_operator_matches_numpy_restatement(case, fused, monkeypatch)
             Xp = [a[(np.arange(len(a)) % 2 == 0) | (np.arange(len(a)) == len(a) - 1)] if len(a) >= 3 else a
                   for a in Xp]
             nlev += 1
-    B = _vcycle_reference(axes, T, mp, 0.1, nlev)
+    B = _vcycle_reference(axes, T, mp, dt, nlev)
     r = rng.standard_normal(n)
     y = rng.standard_normal(n)
     out = []
