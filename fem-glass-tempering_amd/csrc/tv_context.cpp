@@ -432,14 +432,12 @@ int setup_mesh(Ctx* c, const tv_mesh_desc* m) {
   const tv_params& P = c->P;
   for (CgGrid* g = &c->cg; g; g = nullptr) {
     g->dt = P.dt; g->dt_alpha = P.dt * P.alpha; g->dt_f = P.dt * P.f;
-    g->a_rad = 0.001 * (P.sigma * P.epsilon); g->a_conv = 0.001 * P.htc;
-    g->T_amb = P.T_ambient; g->T_amb4 = P.T_ambient * P.T_ambient * P.T_ambient * P.T_ambient;
+    boundary_constants(*g, P);
   }
   {
     DgGrid* g = &c->dg;
     g->dt = P.dt; g->dt_alpha = P.dt * P.alpha; g->dt_f = P.dt * P.f;
-    g->a_rad = 0.001 * (P.sigma * P.epsilon); g->a_conv = 0.001 * P.htc;
-    g->T_amb = P.T_ambient; g->T_amb4 = P.T_ambient * P.T_ambient * P.T_ambient * P.T_ambient;
+    boundary_constants(*g, P);
     g->penalty = 5.0;
   }
   return TV_OK;
@@ -715,6 +713,7 @@ int tv_create(const tv_mesh_desc* mesh, const tv_fe_config* fe, const tv_params*
   c->fam_T = fe->T_family;
   c->fam_S = fe->sigma_family;
   c->P = *params;
+  c->bnd0[0] = params->htc; c->bnd0[1] = params->T_ambient; c->bnd0[2] = params->epsilon;
   if (opts) c->O = *opts;
   else tv_default_options(&c->O);
   if (c->O.model_mode == TV_MODEL_PAPER_EXACT) {
@@ -827,8 +826,7 @@ static int setup_umesh(Ctx* c, const tv_umesh_desc* m, const tv_upart_desc* pd) 
   const tv_params& P = c->P;
   UmGrid& g = c->umg;
   g.dt = P.dt; g.dt_alpha = P.dt * P.alpha; g.dt_f = P.dt * P.f;
-  g.a_rad = 0.001 * (P.sigma * P.epsilon); g.a_conv = 0.001 * P.htc;
-  g.T_amb = P.T_ambient; g.T_amb4 = P.T_ambient * P.T_ambient * P.T_ambient * P.T_ambient;
+  boundary_constants(g, P);
   std::string err;
   const int64_t ndg = m->n_cells * nl;  // DG dofs: device layout [l][cell], host layout cell-major
   if (any_dg && ndg >= (int64_t)INT32_MAX) return c->fail(TV_ERR_ARG, "unstructured meshes: < 2^31 DG dofs");
@@ -890,6 +888,7 @@ static int create_unstructured(const tv_umesh_desc* mesh, const tv_upart_desc* p
   c->fam_T = fe->T_family;
   c->fam_S = fe->sigma_family;
   c->P = *params;
+  c->bnd0[0] = params->htc; c->bnd0[1] = params->T_ambient; c->bnd0[2] = params->epsilon;
   if (opts) c->O = *opts;
   else tv_default_options(&c->O);
   if (c->O.model_mode == TV_MODEL_PAPER_EXACT) {
@@ -1017,6 +1016,7 @@ int tv_destroy(void* ctx) {
   hipSetDevice(c->device);
   if (c->stream) hipStreamSynchronize(c->stream);
   if (c->out) output_destroy(c->out);
+  history_free(c);
   for (int i = 0; i < TV_NUM_FIELDS; ++i)
     if (c->f[i].alloc && c->f[i].base) tv_dev_free(c->f[i].base);
   for (double* p : {c->cr[0], c->cr[1], c->cs[0], c->cs[1], c->cw1, c->wsend, c->dB, c->dtmp, c->Tfo})
@@ -1193,6 +1193,7 @@ int tv_set_initial_condition(void* ctx, double T0) {
   launch_fill(c->f[TV_F_TF].ptr, c->nT, T0, c->stream);
   launch_fill(c->f[TV_F_TF_PARTIAL].ptr, field_stride(c, 0) * 6, T0, c->stream);
   HIPC(hipGetLastError());
+  if (int e = history_reset(c)) return e;  // the step count restarts (no launch unless a history is open)
   HIPC(hipStreamSynchronize(c->stream));
   return TV_OK;
 }

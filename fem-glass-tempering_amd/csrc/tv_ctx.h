@@ -94,6 +94,17 @@ struct AmgLevel {
 // cycles ask for the kind where the hierarchy below level 0 differs.
 enum class Smoother0 { POINT, DG_BLOCK, AUX_BLOCK };
 
+// An open run history (tv_history_open, tv_history.hip): record r, written by
+// kernels queued at the end of the step (r + 1) every, holds
+//   T[P] Tf[P] sigma[P][bs] T_min T_max sigma_min[bs] sigma_max[bs]
+struct History {
+  int n_probes = 0, every = 1, max_records = 0, bs = 1;
+  int64_t rec_len = 0;
+  double* rec = nullptr;      // max_records records, NaN until written
+  double* part = nullptr;     // the extrema pass's per-workgroup (min, max) pairs
+  int64_t* dofs = nullptr;    // device layout: n_probes T dofs, then n_probes sigma dofs
+};
+
 struct Ctx {
   std::string err;
   int device = 0;
@@ -267,6 +278,16 @@ struct Ctx {
   int jac_hint[16] = {0};  // the same for the Jacobi-PCG solves
   int newton_k = 0;
   int newton_pred = 0;  // the previous step's Newton count (speculative residual, newton())
+  // process schedule and run history (tv_history.hip).  steps_done: the steps
+  // tv_step has ended since the last tv_set_initial_condition; bnd0: htc,
+  // T_ambient, epsilon of creation (a NULL schedule table, a cleared schedule);
+  // the stages as tv_set_schedule validated them (sch_end: n_stages - 1 ends)
+  int64_t steps_done = 0;
+  double bnd0[3] = {0.0, 0.0, 0.0};
+  int sch_n = 0;
+  std::vector<int> sch_end;
+  std::vector<double> sch_val[3];
+  History* hist = nullptr;
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -313,6 +334,27 @@ void aux_refresh(Ctx* c, const double* T);
 void aux_smooth(Ctx* c, const PcgState* st, const double* b, double omega, double* x);
 int amg_apply0(Ctx* c, const RedTail* tail);  // a status
 double amg_cycle_bytes(const Ctx* c);
+
+// The Robin constants of a grid struct (CgGrid, DgGrid, UmGrid) from the model
+// parameters: the one place they are derived, at creation and by tv_set_boundary
+template <class Grid>
+inline void boundary_constants(Grid& g, const tv_params& P) {
+  g.a_rad = 0.001 * (P.sigma * P.epsilon); g.a_conv = 0.001 * P.htc;
+  g.T_amb = P.T_ambient; g.T_amb4 = P.T_ambient * P.T_ambient * P.T_ambient * P.T_ambient;
+}
+
+// ---- tv_history.hip ----
+// c->P's htc / T_ambient / epsilon <- the three values, and their constants into
+// every grid struct a launch reads by value (cg, dg, umg, udg.rb, every multigrid level)
+void apply_boundary(Ctx* c, double htc, double T_ambient, double epsilon);
+// tv_step, before its first launch: TV_ERR_STATE if the step would pass an open
+// history's capacity; the schedule's stage of step steps_done + 1
+int history_step_begin(Ctx* c);
+// tv_step, about to return TV_OK: counts the step and, if its end ran (ended) and
+// a record falls on it, queues the record's kernels on the context's stream
+int history_step_end(Ctx* c, bool ended);
+void history_free(Ctx* c);
+int history_reset(Ctx* c);  // tv_set_initial_condition: step count 0, every record NaN again
 
 // ---- tv_context.cpp ----
 void set_global_error(const std::string& m);

@@ -746,14 +746,23 @@ int tv_step(void* ctx, int thermal_only, int* newton_its, int* krylov_its) {
   int conv = 0;
   bool done = false;
   const int step_end = thermal_only ? 2 : 1;
+  // the schedule's stage of this step, before its first evaluation: nothing of a
+  // step is queued before the previous tv_step has returned (the Newton-ahead
+  // queue and the speculative residual work inside newton(), within one step)
+  if (int e = history_step_begin(c)) return e;
   if (int e = newton(c, newton_its, krylov_its, &conv, step_end, &done)) return e;
   // an unconverged solve (error_on_nonconvergence = False) stops here, as the
   // reference's _solve_T assert does (ThermoViscoProblem.py:390): T holds the
   // last Newton iterate, T_prev and the viscoelastic state keep the previous step.
   // Timing runs with fixed iteration counts (ksp_fixed_its > 0, bench.py --share:
   // Newton tolerances 0, so never "converged") end every step as a solve would.
-  if (!done && (conv || c->O.ksp_fixed_its > 0))
+  if (!done && (conv || c->O.ksp_fixed_its > 0)) {
     if (int e = queue_step_end(c, step_end, NewtonGate{})) return e;
+    done = true;
+  }
+  // the step is counted; one that ended is recorded behind its end where a history is open
+  // (an unconverged solve with error_on_nonconvergence = 0 took the step's number and wrote nothing)
+  if (int e = history_step_end(c, done)) return e;
   HIPC(hipGetLastError());
   // no stream synchronisation: the visco update (and T_prev <- T) finishes
   // behind the host, which queues the next step's residual meanwhile (the

@@ -47,6 +47,7 @@ EXPORTS = [
     "tv_ensemble_set_schedule", "tv_ensemble_history_open", "tv_ensemble_history_read",
     "tv_ensemble_create_dg", "tv_ensemble_create_paper",
     "tv_guard_check",
+    "tv_set_boundary", "tv_set_schedule", "tv_step_count", "tv_history_open", "tv_history_read",
 ]
 
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p)
@@ -84,6 +85,11 @@ class EnsembleDesc(C.Structure):
 
 
 class EnsembleSchedule(C.Structure):
+    _fields_ = ([("n_stages", C.c_int), ("stage_end", C.POINTER(C.c_int))]
+                + [(n, C.POINTER(C.c_double)) for n in ("htc", "T_ambient", "epsilon")])
+
+
+class Schedule(C.Structure):
     _fields_ = ([("n_stages", C.c_int), ("stage_end", C.POINTER(C.c_int))]
                 + [(n, C.POINTER(C.c_double)) for n in ("htc", "T_ambient", "epsilon")])
 
@@ -210,6 +216,11 @@ def load_library():
         "tv_ensemble_history_open": (C.c_int, [vp, C.c_int, ip, C.c_int, C.c_int]),
         "tv_ensemble_history_read": (C.c_int, [vp, dp, C.c_size_t, ip]),
         "tv_guard_check": (C.c_int, [i64p, i64p, i64p]),
+        "tv_set_boundary": (C.c_int, [vp, C.c_double, C.c_double, C.c_double]),
+        "tv_set_schedule": (C.c_int, [vp, C.POINTER(Schedule)]),
+        "tv_step_count": (C.c_int, [vp, i64p]),
+        "tv_history_open": (C.c_int, [vp, C.c_int, i64p, i64p, C.c_int, C.c_int]),
+        "tv_history_read": (C.c_int, [vp, dp, C.c_size_t, ip]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -85,6 +85,8 @@ import numpy as np
 
 from . import _native as N
 from .mesh import RectilinearMesh
+# the schedule grammar is shared with ThermoViscoProblem
+from .schedule import STAGE_ENDS, STAGE_KEYS, parse_stages as _parse_stages, stage_tables  # noqa: F401
 
 # model parameters that may differ from bar to bar
 PER_BAR_KEYS = ("htc", "T_0", "T_ambient", "epsilon", "alpha", "f")
@@ -95,33 +97,6 @@ STATE_FIELDS = {"T": 1, "T_prev": 1, "Tf": 1, "Tf_partial": 6, "phi": 1, "xi": 1
 # the fields that live on the stress space (every other state field lives on the temperature space)
 SIGMA_FAMILY = ("sigma", "s_tilde_partial", "sigma_tilde_partial", "s_partial", "sigma_partial")
 _FAMILIES = {"CG": N.TV_CG, "DG": N.TV_DG}
-# what a schedule stage may change, and how it says where it ends
-STAGE_KEYS = ("htc", "T_ambient", "epsilon")
-STAGE_ENDS = ("until", "until_step")
-
-
-def _parse_stages(schedule):
-    """The stages as dicts of scalars / 1D arrays, their keys checked (the sizes
-    and the step grid are checked once n_bars and the time span are known)."""
-    stages = [dict(st) for st in schedule]
-    if not stages:
-        raise ValueError("schedule: at least one stage")
-    for j, st in enumerate(stages):
-        unknown = set(st) - set(STAGE_KEYS) - set(STAGE_ENDS)
-        if unknown:
-            raise ValueError(f"schedule stage {j}: unknown key(s) {sorted(unknown)} "
-                             f"({', '.join(STAGE_ENDS + STAGE_KEYS)})")
-        n_ends = sum(k in st for k in STAGE_ENDS)
-        if j == len(stages) - 1 and n_ends:
-            raise ValueError("schedule: the last stage never ends (no until / until_step)")
-        if j < len(stages) - 1 and n_ends != 1:
-            raise ValueError(f"schedule stage {j}: exactly one of until / until_step (only the last stage has none)")
-        for key, val in st.items():
-            if np.ndim(val) > 1:
-                raise ValueError(f"schedule stage {j}: {key} is a scalar or one value per bar")
-            if np.ndim(val) == 1:
-                st[key] = np.asarray(val, dtype=np.float64)
-    return stages
 
 
 class ThermoViscoEnsemble:
@@ -243,41 +218,8 @@ class ThermoViscoEnsemble:
 
     def _stage_tables(self, stages, mp):
         """(stage_end [n_stages-1][n_bars] or None, {key: [n_stages][n_bars]}) of the parsed stages."""
-        nb, nst = self.n_bars, len(stages)
-        end = np.zeros((nst - 1, nb), dtype=np.intc) if nst > 1 else None
-        for j, st in enumerate(stages[:-1]):
-            if "until_step" in st:
-                k = np.broadcast_to(np.asarray(st["until_step"]), (nb,))
-                if not np.all(np.isfinite(k)) or np.any(k != np.round(k)):
-                    raise ValueError(f"schedule stage {j}: until_step must be whole steps")
-            else:
-                x = (np.broadcast_to(np.asarray(st["until"], dtype=np.float64), (nb,)) - self.time[0]) / self.dt
-                k = np.round(x)
-                off = ~(np.abs(x - k) <= 1e-6)  # also catches NaN
-                if off.any():
-                    b = int(np.argmax(off))
-                    raise ValueError(f"schedule stage {j}: until of bar {b} is not on the step grid "
-                                     f"(time[0] + k dt within 1e-6 dt)")
-            if np.any(k < 0) or np.any(k > np.iinfo(np.intc).max):
-                raise ValueError(f"schedule stage {j}: the stage ends before the start (or out of range) "
-                                 f"for bar {int(np.argmax((k < 0) | (k > np.iinfo(np.intc).max)))}")
-            end[j] = k
-            if j and np.any(end[j] < end[j - 1]):
-                b = int(np.argmax(end[j] < end[j - 1]))
-                raise ValueError(f"schedule: the stage ends of bar {b} decrease at stage {j} "
-                                 f"({int(end[j - 1][b])} then {int(end[j][b])})")
-        tabs = {}
-        for key in STAGE_KEYS:
-            if not any(key in st for st in stages):
-                continue  # NULL table: the creation value in every stage
-            own = self._arrays.get(key, mp[key])  # a missing key takes the bar's model_parameters value
-            tab = np.empty((nst, nb))
-            for j, st in enumerate(stages):
-                tab[j] = st.get(key, own)
-            if not np.all(np.isfinite(tab)):
-                raise ValueError(f"schedule: {key} is not finite")
-            tabs[key] = tab
-        return end, tabs
+        own = {key: self._arrays.get(key, mp[key]) for key in STAGE_KEYS}
+        return stage_tables(stages, self.n_bars, self.time[0], self.dt, own)
 
     def _history_args(self, history):
         unknown = set(history) - {"nodes", "every", "max_records"}

@@ -36,6 +36,7 @@ except Exception:  # pragma: no cover
 from . import _native as N
 from .mesh import RectilinearMesh, UnstructuredMesh, read_msh
 from .models import ThermalModel, ViscoelasticModel
+from .schedule import STAGE_KEYS, parse_stages, stage_tables
 
 _FAMILIES = {"CG": N.TV_CG, "DG": N.TV_DG}
 
@@ -113,7 +114,13 @@ class ThermoViscoProblem:
                  mg_levels: int = 0, dg_kernel: str = "auto", dg_tile_chunk: int = 0,
                  mg_replicate_nodes: int = 0, ksp_fixed_its: int = 0, newton_fixed_its: int = 0,
                  cell_parts=None, mg_coupling: str = "auto", ksp_max_it: int = 10000,
-                 relaxation: str = "taylor") -> None:
+                 relaxation: str = "taylor", schedule=None, history: dict | None = None) -> None:
+        # process schedule and run history: every refusal is decided here, before the
+        # mesh is read or the library is loaded (so a machine without a GPU gets it too)
+        n_steps = ceil((time[1] - time[0]) / dt)
+        self._schedule = None if schedule is None else _schedule_tables(schedule, time[0], dt, model_parameters)
+        self._history = None if history is None else _history_args(history, n_steps)
+        self.history_dofs = None
         if isinstance(mesh_path, (RectilinearMesh, UnstructuredMesh)):
             self.mesh = mesh_path
         elif isinstance(mesh_path, str):
@@ -270,6 +277,15 @@ class ThermoViscoProblem:
         self._ctx = ctx
         try:
             self._apply_relaxation(self.relaxation)
+            if self._schedule is not None:
+                end, tabs = self._schedule
+                sch = N.Schedule()
+                sch.n_stages = len(next(iter(tabs.values())))
+                if end is not None:
+                    sch.stage_end = end.ctypes.data_as(C.POINTER(C.c_int))
+                for key, tab in tabs.items():
+                    setattr(sch, key, tab.ctypes.data_as(C.POINTER(C.c_double)))
+                N.check(lib.tv_set_schedule(ctx, C.byref(sch)), ctx)
         except Exception:
             self.close()
             raise
@@ -336,6 +352,70 @@ class ThermoViscoProblem:
         self._apply_relaxation(relaxation)
         self.relaxation = relaxation
 
+    # ---- process schedule and run history ---------------------------------------------
+    def set_boundary(self, htc=None, T_ambient=None, epsilon=None) -> None:
+        """htc, T_ambient and epsilon of the Robin condition from the next step on; a
+        missing value keeps its current one.  ``physical_model`` follows.  With a
+        ``schedule=`` the schedule's stage overrides this at every step.  The value a
+        Dirichlet ``setup(dirichlet_bc=True)`` took from T_ambient does not follow."""
+        pm = self.physical_model
+        v = [float(getattr(pm, k) if x is None else x) for k, x in zip(STAGE_KEYS, (htc, T_ambient, epsilon))]
+        N.check(self._lib.tv_set_boundary(self._ctx, *v), self._ctx)
+        pm.htc, pm.T_ambient, pm.epsilon = v
+
+    @property
+    def step_count(self) -> int:
+        """Steps taken since ``setup()``: the library's own count (tv_step_count) of the step calls
+        that completed, thermal-only ones included; the schedule's stage and the history's records
+        go by it.  A step that raised NativeError / RuntimeError is not counted."""
+        n = C.c_int64()
+        N.check(self._lib.tv_step_count(self._ctx, C.byref(n)), self._ctx)
+        return n.value
+
+    def _follow_schedule(self) -> None:
+        """physical_model <- the stage the library applies to the step about to run."""
+        end, tabs = self._schedule
+        s = self.step_count + 1
+        j = 0 if end is None else int(np.searchsorted(end, s, side="left"))
+        for key, tab in tabs.items():
+            setattr(self.physical_model, key, float(tab[j]))
+
+    def _open_history(self) -> None:
+        points, dofs, every, max_records = self._history
+        if points is not None:
+            # nearest dof of each space, the lowest index among ties (argmin returns the first)
+            dofs = []
+            for space in (0, 1):
+                X = self._dof_coordinates(space)
+                dofs.append(np.array([np.argmin(((X - p) ** 2).sum(axis=1)) for p in points], dtype=np.int64))
+        dT, dS = (np.ascontiguousarray(d, dtype=np.int64) for d in dofs)
+        i64p = C.POINTER(C.c_int64)
+        N.check(self._lib.tv_history_open(self._ctx, len(dT), dT.ctypes.data_as(i64p), dS.ctypes.data_as(i64p),
+                                          every, max_records), self._ctx)
+        self.history_dofs = {"T": dT, "sigma": dS}
+
+    def get_history(self) -> dict:
+        """The records so far; record r is the state after step ``(r + 1) * every``:
+        ``step``, ``t``, ``T_min``, ``T_max`` of shape (R,), ``T`` and ``Tf`` (R, P),
+        ``sigma`` (R, P, bs), ``sigma_min`` and ``sigma_max`` (R, bs), bs = dim^2.  The
+        extrema run over this partition's owned dofs and skip NaNs (all NaN: NaN).
+        NaN where a step did not end or the history was not yet open."""
+        if self._history is None:
+            raise ValueError("the problem was created without history=")
+        if self.history_dofs is None:
+            raise ValueError("the history is opened by setup()")
+        P, bs, every = len(self.history_dofs["T"]), self.dim * self.dim, self._history[2]
+        n_rec = C.c_int(0)
+        N.check(self._lib.tv_history_read(self._ctx, None, 0, C.byref(n_rec)), self._ctx)
+        out = np.empty((n_rec.value, P * (2 + bs) + 2 + 2 * bs))
+        N.check(self._lib.tv_history_read(self._ctx, out.ctypes.data_as(C.POINTER(C.c_double)), out.size,
+                                          C.byref(n_rec)), self._ctx)
+        step = (np.arange(n_rec.value) + 1) * every
+        e = out[:, P * (2 + bs):]
+        return {"step": step, "t": self.time[0] + step * self.dt, "T": out[:, :P], "Tf": out[:, P:2 * P],
+                "sigma": out[:, 2 * P:P * (2 + bs)].reshape(-1, P, bs), "T_min": e[:, 0], "T_max": e[:, 1],
+                "sigma_min": e[:, 2:2 + bs], "sigma_max": e[:, 2 + bs:]}
+
     def num_dofs(self, space=0):
         n = C.c_int64()
         off = C.c_int64()
@@ -394,6 +474,8 @@ class ThermoViscoProblem:
             # solve as dolfinx NonlinearProblem(bcs=[bc]) applies it
             N.check(self._lib.tv_set_dirichlet(self._ctx, 1, float(self.physical_model.T_ambient)), self._ctx)
         self.dirichlet_bc = bool(dirichlet_bc)
+        if self._history is not None:
+            self._open_history()
         self._outfile_names = (outfile_name, outfile_name1)
         if self.write_output:
             self._write_initial_output(t=self.t)
@@ -462,6 +544,8 @@ class ThermoViscoProblem:
         if self.verbose:
             print(f"t={self.t}")
         self._flush()
+        if self._schedule is not None:
+            self._follow_schedule()
         nits = C.c_int()
         kits = C.c_int()
         rc = self._lib.tv_step(self._ctx, 1 if thermal_only else 0, C.byref(nits), C.byref(kits))
@@ -514,6 +598,63 @@ class ThermoViscoProblem:
             self.close()
         except Exception:
             pass
+
+
+def _schedule_tables(schedule, time0, dt, model_parameters):
+    """(stage_end [n_stages-1] or None, {key: [n_stages]}) of ``schedule=``: the ensemble's
+    grammar for one bar, scalars only."""
+    stages = parse_stages(schedule)
+    for j, st in enumerate(stages):
+        for key, val in st.items():
+            if np.ndim(val) != 0:
+                raise ValueError(f"schedule stage {j}: {key} is a scalar (per-bar arrays belong to ensembles)")
+    own = {key: float(model_parameters[key]) for key in STAGE_KEYS}
+    end, tabs = stage_tables(stages, 1, time0, dt, own)
+    for key in ("htc", "epsilon"):
+        if key in tabs and np.any(tabs[key] < 0):
+            raise ValueError(f"schedule: {key} must not be negative")
+    if not tabs:  # stages that change nothing: still a schedule (the library sees the creation values)
+        tabs = {"htc": np.full((len(stages), 1), own["htc"])}
+    return (None if end is None else np.ascontiguousarray(end[:, 0]),
+            {key: np.ascontiguousarray(tab[:, 0]) for key, tab in tabs.items()})
+
+
+def _history_args(history, n_steps):
+    """(points (P, 3) or None, (T dofs, sigma dofs) or None, every, max_records) of ``history=``."""
+    unknown = set(history) - {"points", "dofs", "every", "max_records"}
+    if unknown:
+        raise ValueError(f"history: unknown key(s) {sorted(unknown)} (points, dofs, every, max_records)")
+    if ("points" in history) == ("dofs" in history):
+        raise ValueError("history: exactly one of points (coordinates) or dofs (dof numbers of get_field)")
+    points = dofs = None
+    if "points" in history:
+        pts = np.asarray(history["points"], dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[0] == 0 or not 1 <= pts.shape[1] <= 3 or not np.all(np.isfinite(pts)):
+            raise ValueError("history: points is a non-empty list of finite [x, y, z] coordinates (1 to 3 each)")
+        points = np.zeros((pts.shape[0], 3))
+        points[:, :pts.shape[1]] = pts
+    else:
+        d = history["dofs"]
+        pair = (d["T"], d["sigma"]) if isinstance(d, dict) and set(d) == {"T", "sigma"} else (d, d)
+        if isinstance(d, dict) and set(d) != {"T", "sigma"}:
+            raise ValueError("history: dofs is a list of dof numbers or dict(T=[...], sigma=[...])")
+        pair = [np.atleast_1d(np.asarray(a)) for a in pair]
+        for a in pair:
+            if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iuf" or np.any(a != np.round(a)):
+                raise ValueError("history: dofs is a non-empty list of dof numbers")
+            if np.any(a < 0):
+                raise ValueError("history: negative probe dof")
+        if pair[0].size != pair[1].size:
+            raise ValueError("history: dofs needs as many T dofs as sigma dofs")
+        dofs = tuple(a.astype(np.int64) for a in pair)
+    every = int(history.get("every", 1))
+    if every < 1:
+        raise ValueError("history: every must be at least 1")
+    max_records = history.get("max_records")
+    max_records = max(n_steps // every, 1) if max_records is None else int(max_records)
+    if max_records < 1:
+        raise ValueError("history: max_records must be at least 1")
+    return points, dofs, every, max_records
 
 
 _SIGMA_FIELDS = {"thermal_strain", "total_strain", "deviatoric_strain", "ds_partial", "dsigma_partial",

@@ -469,6 +469,83 @@ int tv_visco_update(void* ctx);
  * assert(converged), ThermoViscoProblem.py:390) */
 int tv_step(void* ctx, int thermal_only, int* newton_its, int* krylov_its);
 
+/* ---- process schedules and run histories of a single-problem context ----------
+ * (box, unstructured, slab part, unstructured part; the ensembles have
+ * tv_ensemble_set_schedule / tv_ensemble_history_* of their own)
+ *
+ * tv_set_boundary: htc, T_ambient and epsilon of the Robin condition from the
+ * next residual or Jacobian evaluation on (tv_step, tv_solve_T, the operator
+ * calls).  The constants derived from them (0.001 sigma epsilon, 0.001 htc,
+ * T_ambient, T_ambient^4) are kernel arguments held by value in the context's
+ * grid descriptions -- the fine grid of either family, the unstructured
+ * operators, every level of the geometric multigrid, distributed and
+ * replicated levels of a partition included -- and the call rewrites all of
+ * them; no copy lives in device memory and no launch is queued.  Hierarchies
+ * assembled from an operator (TV_PC_AMG, TV_PC_AUX) are not rebuilt: their
+ * coarse operators come from the cell operator alone (the Robin term enters
+ * the fine level only, which follows the change), so they stay valid
+ * preconditioners; the level-0 smoother weights estimated once at the first
+ * solve (DG box multigrid, AMG, AUX) are kept too.  Krylov counts may move.  The value given
+ * to tv_set_dirichlet does NOT follow T_ambient.  All three values must be
+ * finite, htc and epsilon >= 0 (TV_ERR_ARG, nothing changes). */
+int tv_set_boundary(void* ctx, double htc, double T_ambient, double epsilon);
+/* A schedule: the grammar and semantics of tv_ensemble_set_schedule for one
+ * bar.  n_stages >= 1; stage j covers the absolute steps end[j-1] < s <=
+ * end[j] (s 1-based as tv_step_count counts, end[-1] = 0, the last stage never
+ * ends); ends are >= 0 and non-decreasing, equal ends give an empty stage.
+ * stage_end holds n_stages - 1 values (NULL iff n_stages == 1); htc,
+ * T_ambient, epsilon hold n_stages values each, a NULL table meaning the
+ * creation value in every stage.  Table values obey tv_set_boundary's rules.
+ * Everything is validated before any state changes (TV_ERR_ARG).  tv_step
+ * applies the stage of step tv_step_count + 1 as tv_set_boundary would, before
+ * its first evaluation, and only where the stage's values differ from those in
+ * force: the run depends on the absolute step only, not on how the steps are
+ * split over calls, and a schedule that repeats the creation values is the
+ * run without one, bitwise.  While a schedule is set it overrides
+ * tv_set_boundary at every step.  schedule == NULL clears it and puts the
+ * creation values back. */
+typedef struct {
+  int n_stages;
+  const int* stage_end;
+  const double *htc, *T_ambient, *epsilon;
+} tv_schedule;
+int tv_set_schedule(void* ctx, const tv_schedule* schedule);
+/* the steps tv_step has completed -- the calls that returned TV_OK, thermal-only
+ * ones included -- since creation or the last tv_set_initial_condition, which
+ * sets the count to 0.  A call that returns an error (TV_ERR_NOT_CONVERGED,
+ * TV_ERR_KSP, TV_ERR_STATE) is not counted: repeating it repeats the same step
+ * number.  With error_on_nonconvergence = 0 an unconverged solve returns TV_OK
+ * without ending the step (tv_step): it is counted -- it has used its step
+ * number, as a failed bar of an ensemble does -- and a record due at it stays
+ * NaN. */
+int tv_step_count(void* ctx, int64_t* n);
+/* Run history: record r is written after the absolute step (r+1)*every by
+ * kernels queued on the context's stream at the end of that tv_step -- no host
+ * copy, no synchronisation.  A record holds rec_len = n_probes (2 + bs) + 2 +
+ * 2 bs doubles, bs = dim^2:
+ *   T[p], Tf[p] at T_dofs[p]; sigma[p][q] at sigma_dofs[p];
+ *   T_min, T_max; sigma_min[q]; sigma_max[q]
+ * the extrema taken over this context's owned dofs (ghosts excluded, nothing
+ * reduced across ranks) as fmin / fmax take them: a NaN is ignored, an all-NaN
+ * set gives NaN (reference mode's stress, Q5); -0 counts as smaller than +0.
+ * Dof numbers are tv_get_field's (host layout, local to the partition, in [0,
+ * n_owned) of their space; duplicates allowed; TV_ERR_ARG otherwise); both
+ * arrays are required when n_probes >= 1.  The buffer holds max_records
+ * records and is NaN when opened and after tv_set_initial_condition; a step
+ * that does not end writes nothing.  While a history is open tv_step returns
+ * TV_ERR_STATE, before it launches anything, if the step would pass
+ * max_records*every.  Thermal-only steps record what the state holds.
+ * n_probes == 0 closes the history and lifts the cap; opening again replaces
+ * it.  tv_destroy frees it. */
+int tv_history_open(void* ctx, int n_probes, const int64_t* T_dofs, const int64_t* sigma_dofs, int every,
+                    int max_records);
+/* host[n_records][rec_len], n_records = min(tv_step_count / every,
+ * max_records), also stored to *n_records (may be NULL); host == NULL only
+ * asks for n_records.  host holds n_values doubles, at least n_records *
+ * rec_len (TV_ERR_ARG otherwise).  Waits for the stream.  TV_ERR_STATE if no
+ * history is open. */
+int tv_history_read(void* ctx, double* host, size_t n_values, int* n_records);
+
 /* ---- ensembles of independent 1D bars ---------------------------------------
  * A parameter study of the reference's own workload (main.py: one
  * through-thickness bar): n_bars bars with the same cell count, each with its
