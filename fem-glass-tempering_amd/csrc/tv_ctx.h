@@ -72,6 +72,21 @@ struct MgLevel {
   RRArgs rr{};
 };
 
+// One level of the box hierarchy as the cycles walk it (mg_view): level 0 is
+// the context's own grid and vectors (c->cg, the solve's T, r, mgx, w, dinv,
+// mg_omega0), level l >= 1 is c->mg[l - 1].  The ranges are local node ranges
+// along storage axis 2; on one partition off = woff = 0 and n_own = n_win =
+// every node (build_cg_grid: k_begin = w_begin = 0 without ghost planes).
+struct MgView {
+  const CgGrid* g;
+  const double* T;
+  double *b, *x, *w;
+  const double* dinv;
+  double omega;
+  int64_t off, n_own;   // first owned local node, owned node count
+  int64_t woff, n_win;  // the write window (= owned, but on a deep-ghost fine slab)
+};
+
 // level l >= 1 of the algebraic multigrid (tv_amg.cpp): A_l, the prolongation
 // into level l - 1 (rows of that level) and R = P^T; the stored SELL entries
 struct AmgLevel {
@@ -468,14 +483,32 @@ int mg_cycle(Ctx* c, const double* T, const RedTail* tail);
 // copied to h_sums, evn[slot] recorded) behind every batch, gated on the device state
 int pcg_solve_mg(Ctx* c, const double* T, int* its, int* reason, bool post = false);
 KrylovPolicy mg_krylov_policy(Ctx* c);  // of pcg_solve_mg and the two distributed solves
-bool mg_next_level(const std::vector<double> (&Xp)[3], double da, bool automatic, std::vector<double> (&Xc)[3],
-                   std::vector<char> (&is_c)[3], int coarse[3]);
+// One level of the planned box hierarchy (global coordinates): plan[0] is the
+// fine grid; is_c marks the nodes of level l - 1 kept on level l and coarse the
+// axes that coarsen into it
+struct MgPlanLevel {
+  std::vector<double> X[3];
+  std::vector<char> is_c[3];
+  int coarse[3] = {0, 0, 0};
+};
+// the hierarchy below the fine box Xf (mg_levels, or the automatic depth); `have`
+// levels exist before the first planned one (1: the fine grid; 2: a DG1 box's CG1 level too)
+std::vector<MgPlanLevel> mg_plan(const Ctx* c, const std::vector<double> (&Xf)[3], double da, int have);
 void mg_axis_tables(const std::vector<double>& Xf, const std::vector<char>& is_c, std::vector<int>& pi,
                     std::vector<double>& pw, std::vector<int>& ri, std::vector<double>& rw);
+// axis s of the transfer into L: its four tables uploaded, fn / cn / coarse set
+int mg_upload_axis(Ctx* c, MgLevel& L, int s, const std::vector<int>& pi, const std::vector<double>& pw,
+                   const std::vector<int>& ri, const std::vector<double>& rw, int nf, int nc, int coarse);
+int mg_zeroed(Ctx* c, int64_t n, double** out);  // n doubles (>= 1 allocated), zeroed on the stream
 int mg_level_vectors(Ctx* c, MgLevel& L);
 double mg_gershgorin(const std::vector<double> (&X)[3], double dt_alpha);
 double mg_omega(double b);
+MgView mg_view(Ctx* c, size_t l, const double* T0);  // level l; T0: level 0's T
 int mg_level(Ctx* c, size_t l);  // a status
+// level 0's closing step on its owned range: J x, the post-smoothing into z and the (z.z, z.r)
+// records with the tail -- fused into the march where it runs (mg_close0), else J x and k_mg_post
+void mg_close0(Ctx* c, const MgView& v, const RedTail* tail);
+void mg_close0_unfused(Ctx* c, const MgView& v, const RedTail* tail);
 template <class T>
 int mg_upload(Ctx* c, MgLevel& L, const std::vector<T>& h, const T** out) {
   void* p = nullptr;
@@ -489,7 +522,6 @@ int mg_upload(Ctx* c, MgLevel& L, const std::vector<T>& h, const T** out) {
 // ---- tv_mgdist.cpp (GMG on a slab-partitioned box) ----
 int mg_setup_dist(Ctx* c);
 int pcg_solve_mg_dist(Ctx* c, const double* T, int* its, int* reason, bool post = false);
-int mg_prepare_dist(Ctx* c, const double* T);  // slabs of a CG1 box (mg_prepare)
 void fine_window(const Ctx* c, int64_t* off, int64_t* n);
 int mg_cycle_dist(Ctx* c, const double* T, const RedTail* tail);  // slabs of a CG1 box (mg_cycle)
 

@@ -27,6 +27,11 @@
 //     (the prolongation into level l - 1 reads coarse planes either side).
 // The prolongation runs on the fine ghost planes too (its inputs are all
 // local), so level 0's post-smoothing J x needs no exchange of its own.
+//
+// Here: the partitioned set-up (plane owners, local windows, the axis-2 tables
+// over them), the distributed cycle and the two partitioned solves.  The
+// hierarchy plan, the level view, mg_prepare, the replicated levels' mg_level
+// and level 0's closing step are tv_mgsolve.cpp's, shared with one partition.
 #include "tv_ctx.h"
 
 namespace tv {
@@ -58,44 +63,78 @@ void owned_range(const std::vector<int>& own, int p, int* lo, int* hi) {
     }
 }
 
-// level description of one rank
-struct LevelRef {
-  const CgGrid* g;
-  const double* T;
-  double *b, *x, *w;
-  const double* dinv;
-  double omega;
-  int64_t off, n_own;  // first owned local node, owned node count
-  int64_t woff, n_win;  // the write window (= owned, but on a deep-ghost fine slab)
+// A level's planes along storage axis 2 on this rank: the local window
+// [first, first + n) and the owned range [own_lo, own_hi), in global planes
+struct Window2 {
+  int first, n, own_lo, own_hi;
 };
 
-LevelRef level_ref(Ctx* c, size_t l, const double* T0) {
-  LevelRef r{};
-  if (l == 0) {
-    r.g = &c->cg;
-    r.T = T0;
-    r.b = c->r;
-    r.x = c->mgx;
-    r.w = c->w;
-    r.dinv = c->dinv;
-    r.omega = c->mg_omega0;
-  } else {
-    MgLevel& L = c->mg[l - 1];
-    r.g = &L.g;
-    r.T = L.T;
-    r.b = L.b;
-    r.x = L.x;
-    r.w = L.w;
-    r.dinv = L.dinv;
-    r.omega = L.omega;
-  }
-  const int64_t plane = (int64_t)r.g->n0 * r.g->n1;
-  r.off = plane * r.g->k_begin;
-  r.n_own = plane * (r.g->k_end - r.g->k_begin);
-  r.woff = plane * r.g->w_begin;
-  r.n_win = plane * (r.g->w_end - r.g->w_begin);
-  return r;
+// The axis-2 transfer tables between fine window f and coarse window co, cut
+// from the global tables (indexed by global plane) to local plane indices, in
+// place.  GLOBAL coupling: every entry inside the windows keeps its weight; the
+// fine planes outside [fin0, fin1) take no prolongation weight (deep ghosts:
+// the prolongation fills the fine planes within need(l - 1) of the owned ones
+// -- all the post-smoothing J x reads; the outer ghost planes keep x0).
+// LOCAL coupling (block Jacobi): a fine plane interpolates only from the
+// coarse planes this partition owns and a coarse plane restricts only from
+// owned fine planes (R = P^T of the slab).  Excluded entries keep weight 0 and
+// point at a plane inside the window (LOCAL: an owned one) -- finite data.
+int localise_axis2(Ctx* c, const Window2& f, const Window2& co, bool local, int fin0, int fin1,
+                   std::vector<int>& pi, std::vector<double>& pw, std::vector<int>& ri, std::vector<double>& rw) {
+  const int f0 = f.first, c0 = co.first, nf = f.n, nc = co.n;
+  std::vector<int> piL(2 * (size_t)nf), riL(3 * (size_t)nc);
+  std::vector<double> pwL(2 * (size_t)nf), rwL(3 * (size_t)nc);
+  const int cown0 = co.own_lo - c0, cown1 = co.own_hi - c0;
+  const int fown0 = f.own_lo - f0, fown1 = f.own_hi - f0;
+  for (int lf = 0; lf < nf; ++lf)
+    for (int e = 0; e < 2; ++e) {
+      const int cg = pi[2 * (size_t)(f0 + lf) + e] - c0;  // coarse local
+      if (!local && (lf < fin0 || lf >= fin1)) {
+        piL[2 * (size_t)lf + e] = std::min(std::max(cg, 0), nc - 1);
+        pwL[2 * (size_t)lf + e] = 0.0;
+        continue;
+      }
+      const bool ok = local ? (cg >= cown0 && cg < cown1 && lf >= fown0 && lf < fown1) : (cg >= 0 && cg < nc);
+      if (local && !ok) {
+        piL[2 * (size_t)lf + e] = std::min(std::max(cg, cown0), cown1 - 1);
+        pwL[2 * (size_t)lf + e] = 0.0;
+        continue;
+      }
+      // every fine local plane interpolates from coarse local planes (nesting)
+      if (!ok && pw[2 * (size_t)(f0 + lf) + e] != 0.0)
+        return c->fail(TV_ERR_ARG, "partitioned GMG: prolongation leaves the local window (internal)");
+      piL[2 * (size_t)lf + e] = ok ? cg : 0;
+      pwL[2 * (size_t)lf + e] = ok ? pw[2 * (size_t)(f0 + lf) + e] : 0.0;
+    }
+  for (int lc = 0; lc < nc; ++lc)
+    for (int q = 0; q < 3; ++q) {
+      const int fgl = ri[3 * (size_t)(c0 + lc) + q] - f0;  // fine local
+      const bool ok = local ? (fgl >= fown0 && fgl < fown1 && lc >= cown0 && lc < cown1) : (fgl >= 0 && fgl < nf);
+      if (local && !ok) {
+        riL[3 * (size_t)lc + q] = std::min(std::max(fgl, fown0), fown1 - 1);
+        rwL[3 * (size_t)lc + q] = 0.0;
+        continue;
+      }
+      // outside the fine window (a coarse ghost plane's far side, or a coarse
+      // plane of the replicated level away from this slab): weight 0, and the
+      // restriction never writes those planes from this rank's data
+      riL[3 * (size_t)lc + q] = ok ? fgl : std::min(std::max(fgl, 0), nf - 1);
+      rwL[3 * (size_t)lc + q] = ok ? rw[3 * (size_t)(c0 + lc) + q] : 0.0;
+    }
+  pi.swap(piL);
+  pw.swap(pwL);
+  ri.swap(riL);
+  rw.swap(rwL);
+  return TV_OK;
 }
+
+// Transport test only (tv_comm_init_loopback: the neighbours are this slab's
+// periodic images), never part of a real partition's cycle: the ghost planes of
+// x prolongated from the replicated (GLOBAL) level are not the images of the
+// owned ones, so they are refreshed from them -- on a real partition the
+// exchange would deliver exactly what the prolongation computed there (a
+// no-op, never issued).  Call under c->comm_self only.
+int loopback_refresh_periodic_ghosts(Ctx* c, const CgGrid& g, double* x) { return halo_grid(c, g, x); }
 
 }  // namespace
 
@@ -110,47 +149,35 @@ int mg_setup_dist(Ctx* c) {
   std::vector<double> tmp, Xf[3];
   for (int s = 0; s < 3; ++s) Xf[s] = storage_coords(c, s, tmp);
   const double da = c->P.dt * c->P.alpha;
-  HIPC(tv_dev_alloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
-  HIPC(hipMemsetAsync(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
+  if (int e = mg_zeroed(c, c->nT, &c->mgx)) return e;
   c->mg_omega0 = mg_omega(mg_gershgorin(Xf, da));
   // the global hierarchy (the single-partition rule) and the plane owners of every level
-  const int max_levels = c->O.mg_levels > 0 ? c->O.mg_levels : 8;
   const bool automatic = c->O.mg_levels <= 0;
-  struct PlanLevel {
-    std::vector<double> X[3];
-    std::vector<char> is_c[3];  // (l >= 1) fine nodes of level l - 1 kept on level l
-    int coarse[3] = {0, 0, 0};
-    std::vector<int> owner;     // owning part of each global plane (axis 2)
-  };
-  std::vector<PlanLevel> plan(1);
-  for (int s = 0; s < 3; ++s) plan[0].X[s] = Xf[s];
-  plan[0].owner = owners_level0((int)Xf[2].size(), P);
-  for (int lev = 1; lev < max_levels; ++lev) {
-    PlanLevel nl;
-    if (!mg_next_level(plan.back().X, da, automatic, nl.X, nl.is_c, nl.coarse)) break;
-    const PlanLevel& fl = plan.back();
-    for (size_t k = 0; k < fl.X[2].size(); ++k)
-      if (nl.is_c[2][k]) nl.owner.push_back(fl.owner[k]);  // a coarse plane belongs to its fine centre's owner
-    plan.push_back(std::move(nl));
-  }
+  std::vector<MgPlanLevel> plan = mg_plan(c, Xf, da, 1);
+  std::vector<std::vector<int>> owner(plan.size());  // owning part of each global plane (axis 2), per level
+  owner[0] = owners_level0((int)Xf[2].size(), P);
+  for (size_t l = 1; l < plan.size(); ++l)
+    for (size_t k = 0; k < plan[l - 1].X[2].size(); ++k)
+      if (plan[l].is_c[2][k]) owner[l].push_back(owner[l - 1][k]);  // a coarse plane belongs to its fine centre's owner
   // LOCAL coupling with automatic depth: each partition runs its own slab
   // hierarchy, which needs >= 2 planes per level on every partition -- end the
   // hierarchy at the last level where that holds (an explicit mg_levels that
   // goes deeper is refused below)
-  if (local && automatic) {
-    for (size_t l = 1; l < plan.size(); ++l) {
-      int min_own = 1 << 30;
-      for (int q = 0; q < P; ++q) {
-        int lo, hi;
-        owned_range(plan[l].owner, q, &lo, &hi);
-        min_own = std::min(min_own, hi - lo);
-      }
-      if (min_own < 2) {
+  auto min_owned = [&](size_t l) {  // the fewest planes of level l a partition owns
+    int m = 1 << 30;
+    for (int q = 0; q < P; ++q) {
+      int lo, hi;
+      owned_range(owner[l], q, &lo, &hi);
+      m = std::min(m, hi - lo);
+    }
+    return m;
+  };
+  if (local && automatic)
+    for (size_t l = 1; l < plan.size(); ++l)
+      if (min_owned(l) < 2) {
         plan.resize(l);
         break;
       }
-    }
-  }
   const int L = (int)plan.size();
   // the transfers of a partitioned level are the row kernels with table-driven
   // y / z maps (k_mg_restrict_pairs, k_mg_prolong_pairs): x must coarsen
@@ -161,12 +188,7 @@ int mg_setup_dist(Ctx* c) {
   int A = L;
   for (int l = 1; l < L; ++l) {
     const int64_t nodes = (int64_t)plan[l].X[0].size() * plan[l].X[1].size() * plan[l].X[2].size();
-    int min_own = 1 << 30;
-    for (int q = 0; q < P; ++q) {
-      int lo, hi;
-      owned_range(plan[l].owner, q, &lo, &hi);
-      min_own = std::min(min_own, hi - lo);
-    }
+    const int min_own = min_owned((size_t)l);
     const int64_t rep = c->O.mg_replicate_nodes > 0 ? c->O.mg_replicate_nodes : kMgReplicateNodes;
     if (min_own < 2 && local)  // a slab hierarchy needs >= 2 planes per level on every partition
       return c->fail(TV_ERR_ARG, "partitioned GMG (local coupling): a level leaves a partition with < 2 planes; "
@@ -191,7 +213,7 @@ int mg_setup_dist(Ctx* c) {
   // the owned ones (every local plane where the level has one ghost plane)
   auto need = [&](int l) { return (l == 0 && c->mg_cgs) ? 2 : 1; };
   for (int l = 0; l < L; ++l) {
-    owned_range(plan[l].owner, p, &own_lo[l], &own_hi[l]);
+    owned_range(owner[l], p, &own_lo[l], &own_hi[l]);
     if (l < A) {
       const int gd = gdep(l);
       const int glo = p > 0 ? gd : 0, ghi = p < P - 1 ? gd : 0;
@@ -207,7 +229,7 @@ int mg_setup_dist(Ctx* c) {
   for (int l = 1; l < L; ++l) {
     c->mg.emplace_back();
     MgLevel& Lv = c->mg.back();
-    const PlanLevel& pl = plan[l];
+    const MgPlanLevel& pl = plan[l];
     for (int s = 0; s < 3; ++s) Lv.X[s] = pl.X[s];
     Lv.dist = l < A;
     Lv.first2 = first2[l];
@@ -227,158 +249,50 @@ int mg_setup_dist(Ctx* c) {
     Lv.inj1 = own_hi[l] - first2[l];
     // transfer tables (level l - 1 -> l), axes 0 and 1 whole, axis 2 over the local windows
     MgXfer& x = Lv.xf;
-    const PlanLevel& fp = plan[l - 1];
-    int reach_lo = 1 << 30, reach_hi = 0;
+    const MgPlanLevel& fp = plan[l - 1];
+    // GLOBAL: the prolongation fills the local fine planes [fin0, fin1) -- every one (ghost planes included),
+    // but on a deep-ghost level within need(l - 1) planes of the owned ones
+    const int skip = (l - 1 < A) ? std::max(0, gdep(l - 1) - need(l - 1)) : 0;
+    const int fin0 = p > 0 ? skip : 0, fin1 = p < P - 1 ? n2loc[l - 1] - skip : n2loc[l - 1];
     for (int s = 0; s < 3; ++s) {
       std::vector<int> pi, ri;
       std::vector<double> pw, rw;
       mg_axis_tables(fp.X[s], pl.is_c[s], pi, pw, ri, rw);
       int nf = (int)fp.X[s].size(), nc = (int)pl.X[s].size();
       if (s == 2) {
-        const int f0 = first2[l - 1], c0 = first2[l];
-        if (l == A) {  // the coarse planes this rank's owned fine planes restrict to
-          for (int I = 0; I < (int)pl.X[2].size(); ++I)
-            for (int q = 0; q < 3; ++q) {
-              const int f = ri[3 * (size_t)I + q];
-              if (rw[3 * (size_t)I + q] != 0.0 && f >= own_lo[l - 1] && f < own_hi[l - 1]) {
-                reach_lo = std::min(reach_lo, I);
-                reach_hi = std::max(reach_hi, I + 1);
-              }
-            }
-        }
         nf = n2loc[l - 1];
         nc = n2loc[l];
-        std::vector<int> piL(2 * (size_t)nf), riL(3 * (size_t)nc);
-        std::vector<double> pwL(2 * (size_t)nf), rwL(3 * (size_t)nc);
-        // LOCAL coupling (block Jacobi): a fine plane interpolates only from the
-        // coarse planes this partition owns and a coarse plane restricts only
-        // from owned fine planes (R = P^T of the slab); excluded entries keep
-        // weight 0 and point at an owned plane (finite data)
-        const int cown0 = own_lo[l] - c0, cown1 = own_hi[l] - c0;
-        const int fown0 = own_lo[l - 1] - f0, fown1 = own_hi[l - 1] - f0;
-        // deep ghosts: the prolongation fills the fine planes within need(l - 1)
-        // of the owned ones -- all the post-smoothing J x reads; the outer
-        // ghost planes keep x0 and take no weight
-        const int skip = (l - 1 < A) ? std::max(0, gdep(l - 1) - need(l - 1)) : 0;
-        const int fin0 = p > 0 ? skip : 0, fin1 = p < P - 1 ? nf - skip : nf;
-        for (int lf = 0; lf < nf; ++lf)
-          for (int e = 0; e < 2; ++e) {
-            const int cg = pi[2 * (size_t)(f0 + lf) + e] - c0;  // coarse local
-            if (!local && (lf < fin0 || lf >= fin1)) {
-              piL[2 * (size_t)lf + e] = std::min(std::max(cg, 0), nc - 1);
-              pwL[2 * (size_t)lf + e] = 0.0;
-              continue;
-            }
-            const bool ok = local ? (cg >= cown0 && cg < cown1 && lf >= fown0 && lf < fown1) : (cg >= 0 && cg < nc);
-            if (local && !ok) {
-              piL[2 * (size_t)lf + e] = std::min(std::max(cg, cown0), cown1 - 1);
-              pwL[2 * (size_t)lf + e] = 0.0;
-              continue;
-            }
-            // every fine local plane interpolates from coarse local planes (nesting)
-            if (!ok && pw[2 * (size_t)(f0 + lf) + e] != 0.0)
-              return c->fail(TV_ERR_ARG, "partitioned GMG: prolongation leaves the local window (internal)");
-            piL[2 * (size_t)lf + e] = ok ? cg : 0;
-            pwL[2 * (size_t)lf + e] = ok ? pw[2 * (size_t)(f0 + lf) + e] : 0.0;
-          }
-        for (int lc = 0; lc < nc; ++lc)
-          for (int q = 0; q < 3; ++q) {
-            const int fgl = ri[3 * (size_t)(c0 + lc) + q] - f0;  // fine local
-            const bool ok = local ? (fgl >= fown0 && fgl < fown1 && lc >= cown0 && lc < cown1) : (fgl >= 0 && fgl < nf);
-            if (local && !ok) {
-              riL[3 * (size_t)lc + q] = std::min(std::max(fgl, fown0), fown1 - 1);
-              rwL[3 * (size_t)lc + q] = 0.0;
-              continue;
-            }
-            // outside the fine window (a coarse ghost plane's far side, or a coarse
-            // plane of the replicated level away from this slab): weight 0, and the
-            // restriction never writes those planes from this rank's data
-            riL[3 * (size_t)lc + q] = ok ? fgl : std::min(std::max(fgl, 0), nf - 1);
-            rwL[3 * (size_t)lc + q] = ok ? rw[3 * (size_t)(c0 + lc) + q] : 0.0;
-          }
-        pi.swap(piL);
-        pw.swap(pwL);
-        ri.swap(riL);
-        rw.swap(rwL);
+        if (int e = localise_axis2(c, Window2{first2[l - 1], nf, own_lo[l - 1], own_hi[l - 1]},
+                                   Window2{first2[l], nc, own_lo[l], own_hi[l]}, local, fin0, fin1, pi, pw, ri, rw))
+          return e;
       }
-      if (int e = mg_upload(c, Lv, pi, &x.pi[s])) return e;
-      if (int e = mg_upload(c, Lv, pw, &x.pw[s])) return e;
-      if (int e = mg_upload(c, Lv, ri, &x.ri[s])) return e;
-      if (int e = mg_upload(c, Lv, rw, &x.rw[s])) return e;
-      x.fn[s] = nf;
-      x.cn[s] = nc;
-      x.coarse[s] = pl.coarse[s];
+      if (int e = mg_upload_axis(c, Lv, s, pi, pw, ri, rw, nf, nc, pl.coarse[s])) return e;
     }
-    // prolongation into every local fine plane (ghost planes included; LOCAL:
-    // the owned ones, the ghost planes of a slab's V-cycle stay zero)
-    x.f_kb = local ? own_lo[l - 1] - first2[l - 1] : 0;
-    x.f_ke = local ? own_hi[l - 1] - first2[l - 1] : x.fn[2];
-    if (!local && l - 1 < A) {  // deep ghosts: within need(l - 1) planes of the owned fine planes
-      const int skip = std::max(0, gdep(l - 1) - need(l - 1));
-      x.f_kb = p > 0 ? skip : 0;
-      x.f_ke = p < P - 1 ? x.fn[2] - skip : x.fn[2];
-    }
-    if (Lv.dist) {  // restriction: the owned coarse planes
-      x.c_kb = Lv.g.k_begin;
-      x.c_ke = Lv.g.k_end;
-      x.aligned = 0;
-    } else if (l == A) {
-      // restriction into the replicated level: every coarse plane -- the ones
-      // this rank's owned fine planes reach get its masked partial sums (which
-      // add up over the ranks), the others exact zeros (weight-0 entries), so
-      // the level vector needs no zero fill before it (a 4.7 us launch per
-      // V-cycle at the C4 / 8 share)
-      (void)reach_lo;
-      (void)reach_hi;
-      x.c_kb = 0;
-      x.c_ke = x.cn[2];
-      x.aligned = 0;
-    } else {
-      x.c_kb = 0;
-      x.c_ke = x.cn[2];
-      x.aligned = 1;
-    }
+    // prolongation: LOCAL into the owned fine planes (the ghost planes of a slab's V-cycle stay zero)
+    x.f_kb = local ? own_lo[l - 1] - first2[l - 1] : fin0;
+    x.f_ke = local ? own_hi[l - 1] - first2[l - 1] : fin1;
+    // restriction: the owned coarse planes of a distributed level; every plane
+    // of a replicated one.  Into the first replicated level (l == A) the planes
+    // this rank's owned fine planes reach get its masked partial sums (which
+    // add up over the ranks), the others exact zeros (weight-0 entries), so
+    // the level vector needs no zero fill before it (a 4.7 us launch per
+    // V-cycle at the C4 / 8 share)
+    x.c_kb = Lv.dist ? Lv.g.k_begin : 0;
+    x.c_ke = Lv.dist ? Lv.g.k_end : x.cn[2];
+    x.aligned = (Lv.dist || l == A) ? 0 : 1;
   }
   // restriction mask of the last distributed level (ghost planes out)
   if (A < L) {
-    const LevelRef r = level_ref(c, (size_t)(A - 1), nullptr);
+    const MgView r = mg_view(c, (size_t)(A - 1), nullptr);
     const int64_t nloc = (int64_t)r.g->n0 * r.g->n1 * r.g->n2;
     double** m = (A - 1 == 0) ? &c->mg_mask0 : &c->mg[A - 2].mask;
     HIPC(tv_dev_alloc(m, sizeof(double) * (size_t)std::max<int64_t>(1, nloc), kMemDoubles));
     launch_mg_ownmask(nloc, r.off, r.off + r.n_own, nullptr, *m, c->stream);
     HIPC(hipGetLastError());
   }
-  if (c->mg_cgs) {  // s = A p of the single-reduction form
-    HIPC(tv_dev_alloc(&c->mg_s, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
-    HIPC(hipMemsetAsync(c->mg_s, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
-  }
+  if (c->mg_cgs)  // s = A p of the single-reduction form
+    if (int e = mg_zeroed(c, c->nT, &c->mg_s)) return e;
   c->mg_on = true;
-  return TV_OK;
-}
-
-// per Newton iteration: T of every coarse level (distributed levels: injected
-// on the owned planes, then the ghost planes exchanged; the first replicated
-// level: each rank injects its own planes into a zeroed vector, summed over
-// the ranks; below it, injected locally) and the Jacobi diagonals
-int mg_prepare_dist(Ctx* c, const double* T) {
-  const double* Tf = T;
-  for (size_t l = 1; l <= c->mg.size(); ++l) {
-    MgLevel& L = c->mg[l - 1];
-    if (L.dist) {
-      launch_mg_inject_range(L.xf, Tf, L.T, L.inj0, L.inj1, c->stream);
-      if (int e = halo_grid(c, L.g, L.T)) return e;
-    } else if ((int)l == c->mg_A) {
-      HIPC(hipMemsetAsync(L.T, 0, sizeof(double) * (size_t)L.n, c->stream));
-      launch_mg_inject_range(L.xf, Tf, L.T, L.inj0, L.inj1, c->stream);
-      if (int e = allreduce_vec(c, L.T, L.n)) return e;
-    } else {
-      launch_mg_inject(L.xf, Tf, L.T, c->stream);
-    }
-    launch_cg_diag(L.g, L.T, L.dinv, 1, c->stream, L.dinv_interior);
-    L.dinv_interior = true;
-    Tf = L.T;
-  }
-  HIPC(hipGetLastError());
   return TV_OK;
 }
 
@@ -402,7 +316,7 @@ int mg_cycle_dist(Ctx* c, const double* T, const RedTail* tail) {
   const bool deep = c->ghost_depth > 1;
   // ---- down: distributed levels 0 .. A - 1
   for (size_t l = 0; l < ldown; ++l) {
-    const LevelRef r = level_ref(c, l, T);
+    const MgView r = mg_view(c, l, T);
     if (!(deep && l == 0))
       if (int e = vhalo(*r.g, r.x)) return e;  // ghosts of the pre-smoothed x_l
     if (l + 1 == L) break;                           // the coarsest level, distributed: x_l is its solve
@@ -425,38 +339,24 @@ int mg_cycle_dist(Ctx* c, const double* T, const RedTail* tail) {
   }
   // ---- up: prolongation into the distributed levels, post-smoothing, ghosts
   for (size_t l = std::min(A, L - 1); l-- > 0;) {
-    const LevelRef r = level_ref(c, l, T);
+    const MgView r = mg_view(c, l, T);
     MgLevel& C = c->mg[l];
     // every local fine plane, ghost planes included (their inputs are local)
     launch_mg_prolong(C.xf, c->st, r.x, C.x, l == 0 ? dmask : nullptr, s);
-    // loopback transport test only (tv_comm_init_loopback: the neighbours are
-    // this slab's periodic images): the ghost planes prolongated from the
-    // replicated GLOBAL level are not the images of the owned ones, so they are
-    // refreshed from them -- on a real partition the exchange would deliver
-    // exactly what the prolongation computed there (a no-op, never issued)
     if (c->comm_self && l + 1 == A && A < L)
-      if (int e = vhalo(*r.g, r.x)) return e;
-    // level 0: J x, the post-smoothing and the (z.z, z.r) records in the march
-    // epilogue (+ the side-face pass with the reduction tail), as on one partition
-    if (l == 0 && launch_cg_japply_post(*r.g, r.T, r.x, r.b, r.dinv, r.omega, c->z, c->st, c->partials, tail, s) >= 0)
-      return TV_OK;
-    launch_cg_japply_partial(*r.g, r.T, r.x, r.w, c->st, s);
-    const FaceAdd fa = cg_face_add(*r.g, r.off);
-    if (l > 0) {
-      launch_mg_jacobi(r.n_own, c->st, r.b + r.off, r.w + r.off, &fa, r.dinv + r.off, r.omega, r.x + r.off, 1, s);
-      if (int e = vhalo(*r.g, r.x)) return e;
-    } else {
-      launch_mg_post(r.n_own, c->st, r.x + r.off, r.b + r.off, r.w + r.off, &fa, r.dinv + r.off, r.omega,
-                     c->z + r.off, c->partials, tail, s);
+      if (int e = loopback_refresh_periodic_ghosts(c, *r.g, r.x)) return e;
+    if (l == 0) {  // J x, the post-smoothing and the (z.z, z.r) records, as on one partition
+      mg_close0(c, r, tail);
       return TV_OK;
     }
+    launch_cg_japply_partial(*r.g, r.T, r.x, r.w, c->st, s);
+    const FaceAdd fa = cg_face_add(*r.g, r.off);
+    launch_mg_jacobi(r.n_own, c->st, r.b + r.off, r.w + r.off, &fa, r.dinv + r.off, r.omega, r.x + r.off, 1, s);
+    if (int e = vhalo(*r.g, r.x)) return e;
   }
-  // no coarse level: the two smoothing steps of level 0 only
-  const LevelRef r = level_ref(c, 0, T);
-  launch_cg_japply_partial(*r.g, r.T, r.x, r.w, c->st, s);
-  const FaceAdd fa = cg_face_add(*r.g, r.off);
-  launch_mg_post(r.n_own, c->st, r.x + r.off, r.b + r.off, r.w + r.off, &fa, r.dinv + r.off, r.omega,
-                 c->z + r.off, c->partials, tail, s);
+  // no coarse level: the two smoothing steps of level 0 only (never the march
+  // epilogue's fused form here)
+  mg_close0_unfused(c, mg_view(c, 0, T), tail);
   return TV_OK;
 }
 

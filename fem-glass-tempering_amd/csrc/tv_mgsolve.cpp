@@ -1,6 +1,12 @@
 // Geometric multigrid on the box hierarchy: setup, per-Newton preparation and
 // the multigrid-preconditioned KSPCG (the reference's PCGAMG,
 // ThermoViscoProblem.py:343-346, replaced for rectilinear 3D meshes).
+//
+// Here, shared by every box cycle: the hierarchy plan and transfer tables, the
+// level view (mg_view: level 0 is a level), mg_prepare for every configuration,
+// the restriction step, the coarse levels' mg_level, level 0's closing step and
+// smoother; and the cycle and solve of one partition and of a DG1 slab.
+// tv_mgdist.cpp: the slab-partitioned CG1 box's set-up, cycle and solves.
 #include <cstdlib>
 
 #include "tv_ctx.h"
@@ -180,8 +186,8 @@ int level0_weight(Ctx* c, const double* T) {
 // count is odd (coarse nodes are a subset of the fine ones); stop where the
 // operator is mass-dominated (dt alpha / h^2 <= 0.5 with h the smallest mean
 // cell length: a Jacobi step is then a good solve) or nothing coarsens.
-bool mg_next_level(const std::vector<double> (&Xp)[3], double da, bool automatic, std::vector<double> (&Xc)[3],
-                   std::vector<char> (&is_c)[3], int coarse[3]) {
+static bool mg_next_level(const std::vector<double> (&Xp)[3], double da, bool automatic,
+                          std::vector<double> (&Xc)[3], std::vector<char> (&is_c)[3], int coarse[3]) {
   double h = 1e300;
   bool any = false;
   for (int s = 0; s < 3; ++s) {
@@ -204,6 +210,19 @@ bool mg_next_level(const std::vector<double> (&Xp)[3], double da, bool automatic
       if (is_c[s][i]) Xc[s].push_back(Xp[s][i]);
   }
   return true;
+}
+
+std::vector<MgPlanLevel> mg_plan(const Ctx* c, const std::vector<double> (&Xf)[3], double da, int have) {
+  const int max_levels = c->O.mg_levels > 0 ? c->O.mg_levels : 8;
+  const bool automatic = c->O.mg_levels <= 0;
+  std::vector<MgPlanLevel> plan(1);
+  for (int s = 0; s < 3; ++s) plan[0].X[s] = Xf[s];
+  for (int lev = have; lev < max_levels; ++lev) {
+    MgPlanLevel nl;
+    if (!mg_next_level(plan.back().X, da, automatic, nl.X, nl.is_c, nl.coarse)) break;
+    plan.push_back(std::move(nl));
+  }
+  return plan;
 }
 
 // Transfer tables of one axis over the whole (global) axis: prolongation = two
@@ -248,6 +267,19 @@ void mg_axis_tables(const std::vector<double>& Xf, const std::vector<char>& is_c
       rw[3 * I + 2] = pw[2 * (fc + 1)];  // fine fc + 1: its left coarse neighbour is I
     }
   }
+}
+
+int mg_upload_axis(Ctx* c, MgLevel& L, int s, const std::vector<int>& pi, const std::vector<double>& pw,
+                   const std::vector<int>& ri, const std::vector<double>& rw, int nf, int nc, int coarse) {
+  MgXfer& x = L.xf;
+  if (int e = mg_upload(c, L, pi, &x.pi[s])) return e;
+  if (int e = mg_upload(c, L, pw, &x.pw[s])) return e;
+  if (int e = mg_upload(c, L, ri, &x.ri[s])) return e;
+  if (int e = mg_upload(c, L, rw, &x.rw[s])) return e;
+  x.fn[s] = nf;
+  x.cn[s] = nc;
+  x.coarse[s] = coarse;
+  return TV_OK;
 }
 
 // Tables of the fused residual restriction (RRArgs) along one axis: for coarse
@@ -347,6 +379,13 @@ static unsigned rr_levels(int64_t fine_nodes) {
   return fine_nodes >= kRRMinNodes ? 1u : 0u;
 }
 
+int mg_zeroed(Ctx* c, int64_t n, double** out) {
+  const size_t bytes = sizeof(double) * (size_t)std::max<int64_t>(1, n);
+  HIPC(tv_dev_alloc(out, bytes, kMemDoubles));
+  HIPC(hipMemsetAsync(*out, 0, bytes, c->stream));
+  return TV_OK;
+}
+
 // T, b, x, w, dinv of a level (local size L.n), zeroed
 int mg_level_vectors(Ctx* c, MgLevel& L) {
   const CgGrid& f = c->cg;  // thermal constants (set by setup_mesh for both families)
@@ -354,11 +393,8 @@ int mg_level_vectors(Ctx* c, MgLevel& L) {
   L.g.a_rad = f.a_rad; L.g.a_conv = f.a_conv; L.g.T_amb = f.T_amb; L.g.T_amb4 = f.T_amb4;
   L.n = (int64_t)L.g.n0 * L.g.n1 * L.g.n2;
   for (double** q : {&L.T, &L.b, &L.x, &L.w, &L.dinv}) {
-    void* p = nullptr;
-    HIPC(tv_dev_alloc(&p, sizeof(double) * (size_t)std::max<int64_t>(1, L.n), kMemDoubles));
-    HIPC(hipMemsetAsync(p, 0, sizeof(double) * (size_t)std::max<int64_t>(1, L.n), c->stream));
-    L.bufs.push_back(p);
-    *q = static_cast<double*>(p);
+    if (int e = mg_zeroed(c, L.n, q)) return e;
+    L.bufs.push_back(*q);
   }
   return TV_OK;
 }
@@ -379,8 +415,7 @@ int mg_setup(Ctx* c) {
   std::vector<double> tmp, Xf[3];
   for (int s = 0; s < 3; ++s) Xf[s] = storage_coords(c, s, tmp);
   const double da = c->P.dt * c->P.alpha;
-  HIPC(tv_dev_alloc(&c->mgx, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), kMemDoubles));
-  HIPC(hipMemsetAsync(c->mgx, 0, sizeof(double) * (size_t)std::max<int64_t>(1, c->nT), c->stream));
+  if (int e = mg_zeroed(c, c->nT, &c->mgx)) return e;
   if (dg) {
     // level 1: the CG1 space of the same box (two-level DG -> CG, then the CG hierarchy)
     c->smoother0 = Smoother0::DG_BLOCK;
@@ -390,15 +425,10 @@ int mg_setup(Ctx* c) {
   } else {
     c->mg_omega0 = mg_omega(mg_gershgorin(Xf, da));
   }
-  const int max_levels = c->O.mg_levels > 0 ? c->O.mg_levels : 8;
-  const bool automatic = c->O.mg_levels <= 0;
-  std::vector<double> Xp[3] = {Xf[0], Xf[1], Xf[2]};
-  for (int lev = 1 + (dg ? 1 : 0); lev < max_levels; ++lev) {
-    std::vector<double> Xc[3];
-    std::vector<char> is_c[3];  // fine node kept on this level
-    int coarse[3];
-    if (!mg_next_level(Xp, da, automatic, Xc, is_c, coarse)) break;
-    if (int e = mg_add_cg_level(c, Xc, da)) return e;
+  const std::vector<MgPlanLevel> plan = mg_plan(c, Xf, da, dg ? 2 : 1);
+  for (size_t l = 1; l < plan.size(); ++l) {
+    const std::vector<double>(&Xp)[3] = plan[l - 1].X;
+    if (int e = mg_add_cg_level(c, plan[l].X, da)) return e;
     MgLevel& L = c->mg.back();
     // transfer maps (finer level Xp -> this level)
     MgXfer& x = L.xf;
@@ -407,14 +437,10 @@ int mg_setup(Ctx* c) {
     for (int s = 0; s < 3; ++s) {
       std::vector<int> pi;
       std::vector<double> pw;
-      mg_axis_tables(Xp[s], is_c[s], pi, pw, ri[s], rw[s]);
-      if (int e = mg_upload(c, L, pi, &x.pi[s])) return e;
-      if (int e = mg_upload(c, L, pw, &x.pw[s])) return e;
-      if (int e = mg_upload(c, L, ri[s], &x.ri[s])) return e;
-      if (int e = mg_upload(c, L, rw[s], &x.rw[s])) return e;
-      x.fn[s] = (int)Xp[s].size();
-      x.cn[s] = (int)L.X[s].size();
-      x.coarse[s] = coarse[s];
+      mg_axis_tables(Xp[s], plan[l].is_c[s], pi, pw, ri[s], rw[s]);
+      if (int e = mg_upload_axis(c, L, s, pi, pw, ri[s], rw[s], (int)Xp[s].size(), (int)L.X[s].size(),
+                                 plan[l].coarse[s]))
+        return e;
     }
     x.f_kb = 0;
     x.f_ke = x.fn[2];
@@ -426,71 +452,86 @@ int mg_setup(Ctx* c) {
     const size_t from = c->mg.size() - 1 - (dg ? 1 : 0);  // index of the finer level (0: the fine grid)
     if (!dg && ((rr_levels(c->nT) >> from) & 1u))
       if (int e = rr_setup(c, L, Xp, ri, rw)) return e;
-    for (int s = 0; s < 3; ++s) Xp[s] = L.X[s];
   }
   c->mg_on = true;
   return TV_OK;
 }
 
-// per Newton iteration: T injected down the hierarchy (DG: the vertex mean of
-// the cell-local values onto the CG level, and the facet means of level 0's
-// cell blocks), coarse Jacobi diagonals
-int mg_prepare(Ctx* c, const double* T) {
-  if (c->amg_on) return TV_OK;  // the algebraic hierarchy is T-independent (tv_amg.cpp)
+// Level 1 of a DG1 box at T: the vertex mean of the cell-local values (a slab:
+// on its owned vertex planes, summed over the slabs -- each plane from one
+// slab), and the facet means of level 0's cell blocks
+static int mg_dg_level1_T(Ctx* c, const double* T, MgLevel& L) {
+  const bool slab = c->n_parts > 1;
+  if (slab) HIPC(hipMemsetAsync(L.T, 0, sizeof(double) * (size_t)L.n, c->stream));
+  launch_mg_dg_T(c->dg, T, L.T, c->plane_begin - c->dg.k_begin, c->stream);  // 0 on one partition
+  if (slab)
+    if (int e = allreduce_vec(c, L.T, L.n)) return e;
+  launch_dg_gface(c->dg, T, c->dggface, c->stream);
+  return TV_OK;
+}
+
+// T onto every level from the one above, one level at a time, and the level's
+// Jacobi diagonal.  How T reaches a level: a DG1 box's level 1 as above; a
+// distributed level of a CG1 slab (tv_mgdist.cpp) injected on the owned planes,
+// then the ghost planes exchanged; its first replicated level: each rank
+// injects its own planes into a zeroed vector, summed over the ranks; every
+// other level injected locally
+static int mg_inject_levels(Ctx* c, const double* T) {
   const bool dg = c->smoother0 == Smoother0::DG_BLOCK;
-  if (c->n_parts > 1 && !dg) return mg_prepare_dist(c, T);  // slabs of a CG1 box (tv_mgdist.cpp)
-  // a DG1 slab: level 1 onwards is replicated (mg_setup); its T = the vertex
-  // means on the slab's owned vertex planes, summed over the slabs (each plane from one slab)
-  const bool dgpart = dg && c->n_parts > 1;
-  auto dg_T = [&](MgLevel& L) -> int {
-    if (!dgpart) {
-      launch_mg_dg_T(c->dg, T, L.T, 0, c->stream);
-      return TV_OK;
-    }
-    HIPC(hipMemsetAsync(L.T, 0, sizeof(double) * (size_t)L.n, c->stream));
-    launch_mg_dg_T(c->dg, T, L.T, c->plane_begin - c->dg.k_begin, c->stream);
-    return allreduce_vec(c, L.T, L.n);
-  };
-  // after the first call (dinv interiors in place): the CG levels below the
-  // base in two launches (launch_mg_prepare)
-  const size_t base = dg ? 1 : 0;  // DG: level 1 is the vertex mean of the DG field
-  const size_t ncg = c->mg.size() - std::min(c->mg.size(), base);
-  bool ready = ncg > 0 && ncg <= (size_t)kMgPrepMax;
-  for (size_t l = base; l < c->mg.size() && ready; ++l)
-    ready = c->mg[l].dinv_interior && cg_uses_march(c->mg[l].g) && c->mg[l].g.bnodes != nullptr;
-  if (ready) {
-    if (base == 1) {
-      MgLevel& L = c->mg[0];
-      if (int e = dg_T(L)) return e;
-      launch_dg_gface(c->dg, T, c->dggface, c->stream);
-      launch_cg_diag(L.g, L.T, L.dinv, 1, c->stream, true);
-    }
-    MgPrep p{};
-    p.nlev = (int)ncg;
-    p.Tbase = base == 1 ? c->mg[0].T : T;
-    for (size_t i = 0; i < ncg; ++i) {
-      MgLevel& L = c->mg[base + i];
-      p.xf[i] = L.xf;
-      p.T[i] = L.T;
-      p.dinv[i] = L.dinv;
-      p.g[i] = L.g;
-      p.off_n[i + 1] = p.off_n[i] + (L.n + 63) / 64 * 64;
-      p.off_b[i + 1] = p.off_b[i] + (L.g.n_bnodes + 63) / 64 * 64;
-    }
-    launch_mg_prepare(p, c->stream);
-    return TV_OK;
-  }
   const double* Tf = T;
   for (size_t l = 0; l < c->mg.size(); ++l) {
     MgLevel& L = c->mg[l];
     if (l == 0 && dg) {
-      if (int e = dg_T(L)) return e;
-      launch_dg_gface(c->dg, T, c->dggface, c->stream);
-    } else launch_mg_inject(L.xf, Tf, L.T, c->stream);
+      if (int e = mg_dg_level1_T(c, T, L)) return e;
+    } else if (L.dist) {
+      launch_mg_inject_range(L.xf, Tf, L.T, L.inj0, L.inj1, c->stream);
+      if (int e = halo_grid(c, L.g, L.T)) return e;
+    } else if (c->n_parts > 1 && !dg && (int)l + 1 == c->mg_A) {
+      HIPC(hipMemsetAsync(L.T, 0, sizeof(double) * (size_t)L.n, c->stream));
+      launch_mg_inject_range(L.xf, Tf, L.T, L.inj0, L.inj1, c->stream);
+      if (int e = allreduce_vec(c, L.T, L.n)) return e;
+    } else {
+      launch_mg_inject(L.xf, Tf, L.T, c->stream);
+    }
     launch_cg_diag(L.g, L.T, L.dinv, 1, c->stream, L.dinv_interior);
     L.dinv_interior = true;
     Tf = L.T;
   }
+  HIPC(hipGetLastError());
+  return TV_OK;
+}
+
+// per Newton iteration: T down the hierarchy and the coarse Jacobi diagonals
+int mg_prepare(Ctx* c, const double* T) {
+  if (c->amg_on) return TV_OK;  // the algebraic hierarchy is T-independent (tv_amg.cpp)
+  const bool dg = c->smoother0 == Smoother0::DG_BLOCK;
+  // every level a whole box (one partition, and a DG1 slab's replicated levels),
+  // after the first call (dinv interiors in place): the CG levels below the
+  // base in two launches (launch_mg_prepare)
+  const size_t base = dg ? 1 : 0;  // DG: level 1 is the vertex mean of the DG field
+  const size_t ncg = c->mg.size() - std::min(c->mg.size(), base);
+  bool ready = (c->n_parts == 1 || dg) && ncg > 0 && ncg <= (size_t)kMgPrepMax;
+  for (size_t l = base; l < c->mg.size() && ready; ++l)
+    ready = c->mg[l].dinv_interior && cg_uses_march(c->mg[l].g) && c->mg[l].g.bnodes != nullptr;
+  if (!ready) return mg_inject_levels(c, T);
+  if (base == 1) {
+    MgLevel& L = c->mg[0];
+    if (int e = mg_dg_level1_T(c, T, L)) return e;
+    launch_cg_diag(L.g, L.T, L.dinv, 1, c->stream, true);
+  }
+  MgPrep p{};
+  p.nlev = (int)ncg;
+  p.Tbase = base == 1 ? c->mg[0].T : T;
+  for (size_t i = 0; i < ncg; ++i) {
+    MgLevel& L = c->mg[base + i];
+    p.xf[i] = L.xf;
+    p.T[i] = L.T;
+    p.dinv[i] = L.dinv;
+    p.g[i] = L.g;
+    p.off_n[i + 1] = p.off_n[i] + (L.n + 63) / 64 * 64;
+    p.off_b[i + 1] = p.off_b[i] + (L.g.n_bnodes + 63) / 64 * 64;
+  }
+  launch_mg_prepare(p, c->stream);
   return TV_OK;
 }
 
@@ -509,39 +550,80 @@ void mg_prolong_from(Ctx* c, size_t ci, double* xf, const double* mask) {
   }
 }
 
-static const char kRRChunkMsg[] = "GMG: fused residual restriction refused (march chunk out of range)";
+MgView mg_view(Ctx* c, size_t l, const double* T0) {
+  const MgLevel* L = l ? &c->mg[l - 1] : nullptr;
+  MgView r = L ? MgView{&L->g, L->T, L->b, L->x, L->w, L->dinv, L->omega}
+               : MgView{&c->cg, T0, c->r, c->mgx, c->w, c->dinv, c->mg_omega0};
+  const int64_t plane = (int64_t)r.g->n0 * r.g->n1;
+  r.off = plane * r.g->k_begin;
+  r.n_own = plane * (r.g->k_end - r.g->k_begin);
+  r.woff = plane * r.g->w_begin;
+  r.n_win = plane * (r.g->w_end - r.g->w_begin);
+  return r;
+}
+
+// The residual of fine level f (a whole box: one partition, or a replicated
+// level) restricted into the next coarser level C, with C's pre-smoothing step
+// from 0 (x = omega D^-1 b): b_C = R (b - J x), three ways.  mask: the transfer
+// mask (level 0 under Dirichlet: the free subspace; else null).  fold_faces: the
+// restriction may add the face-workgroup facet terms itself (no k_cg_addfaces;
+// a per-node facet term inside the 27-point gather measured slower) -- one
+// launch fewer where the V-cycle is launch-bound; level 0 allows it below
+// kMgFoldFacesNodes (at C4 a complete J x measured the same).
+static int mg_restrict_into(Ctx* c, const MgView& f, MgLevel& C, const double* mask, bool fold_faces) {
+  hipStream_t s = c->stream;
+  const FaceAdd fa = cg_face_add(*f.g, 0);
+  if (C.rr.on && mask == nullptr && fa.on) {
+    // without J x: the facet terms of x on every face, then the fused residual
+    // restriction (RRArgs)
+    launch_cg_facet_faces(*f.g, f.T, f.x, c->st, s);
+    if (!launch_mg_rrestrict(C.rr, c->st, f.b, f.x, cg_face_add_all(*f.g), C.b, C.dinv, C.omega, C.x, s))
+      return c->fail(TV_ERR_STATE, "GMG: fused residual restriction refused (march chunk out of range)");
+  } else if (fa.on && mg_restrict_folds_faces(C.xf) && fold_faces) {
+    launch_cg_japply_partial(*f.g, f.T, f.x, f.w, c->st, s);
+    launch_mg_restrict(C.xf, c->st, f.b, f.w, &fa, mask, C.b, C.dinv, C.omega, C.x, s);
+  } else {  // the complete J x (k_cg_addfaces)
+    launch_cg_japply(*f.g, f.T, f.x, f.w, nullptr, nullptr, s, c->st);
+    launch_mg_restrict(C.xf, c->st, f.b, f.w, nullptr, mask, C.b, C.dinv, C.omega, C.x, s);
+  }
+  return TV_OK;
+}
 
 // V-cycle on coarse level l >= 1 (index l - 1 in c->mg): rhs b -> x; the
 // pre-smoothing step from 0 (x = omega D^-1 b) was formed by the restriction
-// that produced b.  The J x before the restriction is complete (k_cg_addfaces:
-// a per-node facet term inside the 27-point gather measured slower); the one
-// before the post-smoothing leaves the facet terms of the faces along the
-// march to that pointwise consumer (FaceAdd).
+// that produced b.  The J x before the post-smoothing leaves the facet terms
+// of the faces along the march to that pointwise consumer (FaceAdd).
 int mg_level(Ctx* c, size_t l) {
   MgLevel& L = c->mg[l - 1];
   hipStream_t s = c->stream;
   if (l < c->mg.size()) {
-    const MgLevel& C = c->mg[l];
-    const FaceAdd fa = cg_face_add(L.g, 0);
-    if (C.rr.on && fa.on) {  // fused residual restriction (no J x of this level)
-      launch_cg_facet_faces(L.g, L.T, L.x, c->st, s);
-      if (!launch_mg_rrestrict(C.rr, c->st, L.b, L.x, cg_face_add_all(L.g), C.b, C.dinv, C.omega, C.x, s))
-        return c->fail(TV_ERR_STATE, kRRChunkMsg);
-    } else if (fa.on && mg_restrict_folds_faces(C.xf)) {  // the restriction adds the facet terms (no k_cg_addfaces)
-      launch_cg_japply_partial(L.g, L.T, L.x, L.w, c->st, s);
-      launch_mg_restrict(C.xf, c->st, L.b, L.w, &fa, nullptr, C.b, C.dinv, C.omega, C.x, s);
-    } else {
-      launch_cg_japply(L.g, L.T, L.x, L.w, nullptr, nullptr, s, c->st);
-      launch_mg_restrict(C.xf, c->st, L.b, L.w, nullptr, nullptr, C.b, C.dinv, C.omega, C.x, s);
-    }
+    if (int e = mg_restrict_into(c, mg_view(c, l, nullptr), c->mg[l], nullptr, true)) return e;
     if (int e = mg_level(c, l + 1)) return e;
     mg_prolong_from(c, l, L.x, nullptr);
     launch_cg_japply_partial(L.g, L.T, L.x, L.w, c->st, s);
     // post-smoothing, unless the prolongation out of this level applies it (mg_prolong_from)
-    if (!mg_prolong_smooths(L.xf))
+    if (!mg_prolong_smooths(L.xf)) {
+      const FaceAdd fa = cg_face_add(L.g, 0);
       launch_mg_jacobi(L.n, c->st, L.b, L.w, &fa, L.dinv, L.omega, L.x, 1, s);
+    }
   }
   return TV_OK;
+}
+
+void mg_close0_unfused(Ctx* c, const MgView& v, const RedTail* tail) {
+  hipStream_t s = c->stream;
+  launch_cg_japply_partial(*v.g, v.T, v.x, v.w, c->st, s);
+  const FaceAdd fa = cg_face_add(*v.g, v.off);
+  launch_mg_post(v.n_own, c->st, v.x + v.off, v.b + v.off, v.w + v.off, &fa, v.dinv + v.off, v.omega, c->z + v.off,
+                 c->partials, tail, s);
+}
+
+void mg_close0(Ctx* c, const MgView& v, const RedTail* tail) {
+  // J x, post-smoothing and (z.z, z.r) in the march epilogue (+ the side-face
+  // pass with the reduction tail), on one partition and on a slab alike
+  if (launch_cg_japply_post(*v.g, v.T, v.x, v.b, v.dinv, v.omega, c->z, c->st, c->partials, tail, c->stream) >= 0)
+    return;
+  mg_close0_unfused(c, v, tail);
 }
 
 // Dirichlet mode constrains a CG1 temperature only (a DG1 dof belongs to no
@@ -555,60 +637,38 @@ static bool dirichlet_masks(const Ctx* c) { return c->dir_on && c->fam_T == TV_C
 // c->mgx (level0_update); coarse correction, post-smoothing into z with the
 // (z.z, z.r) reduction tail
 static int mg_cycle_box(Ctx* c, const double* T, const RedTail* tail) {
-  const int64_t n = c->nT;
   hipStream_t s = c->stream;
   const double* mask = dirichlet_masks(c) ? c->dinv : nullptr;  // Dirichlet: the free subspace
   // DG1 level 0: complete DG J x (Robin facets inline), vertex sums / injection to CG1
   if (c->smoother0 == Smoother0::DG_BLOCK) {
     const DgGrid& d = c->dg;
     MgLevel& C = c->mg[0];
-    if (c->n_parts > 1) {  // a slab (mg_setup): the replicated level 1, see there
-      const int kg0 = c->plane_begin - d.k_begin;
+    const bool slab = c->n_parts > 1;  // the replicated level 1 (mg_setup), see there
+    const int kg0 = c->plane_begin - d.k_begin;  // 0 on one partition
+    if (slab)
       if (int e = halo(c, c->mgx)) return e;  // x0 of the ghost layers (J x0, the prolongation into them)
-      launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
+    launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
+    if (slab) {  // the slabs' partial restrictions summed, then level 1's pre-smoothing from 0
       HIPC(hipMemsetAsync(C.b, 0, sizeof(double) * (size_t)C.n, s));
       launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, nullptr, 0.0, nullptr, kg0, s);
       if (int e = allreduce_vec(c, C.b, C.n)) return e;
-      launch_mg_jacobi(C.n, c->st, C.b, nullptr, nullptr, C.dinv, C.omega, C.x, 0, s);  // pre-smoothing from 0
-      if (int e = mg_level(c, 1)) return e;
-      launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, kg0, s);
+      launch_mg_jacobi(C.n, c->st, C.b, nullptr, nullptr, C.dinv, C.omega, C.x, 0, s);
     } else {
-      launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
-      launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, C.dinv, C.omega, C.x, 0, s);
-      if (int e = mg_level(c, 1)) return e;
-      launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, 0, s);
+      launch_mg_dg_restrict(d, c->st, c->r, c->w, mask, C.b, C.dinv, C.omega, C.x, kg0, s);
     }
+    if (int e = mg_level(c, 1)) return e;
+    launch_mg_dg_prolong(d, c->st, c->mgx, C.x, mask, kg0, s);
     launch_dg_japply(d, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
     launch_dg_bpost(d, c->st, c->mgx, c->r, c->w, c->dggface, c->mg_omega0, c->z, c->partials, tail, s);
     return TV_OK;
   }
-  const FaceAdd fa = cg_face_add(c->cg, 0);
+  const MgView v = mg_view(c, 0, T);
   if (!c->mg.empty()) {
-    MgLevel& C = c->mg[0];
-    // below kMgFoldFacesNodes the restriction adds the face-workgroup facet
-    // terms itself, as on the coarse levels (one launch fewer where the V-cycle
-    // is launch-bound); at C4 a complete J x (k_cg_addfaces) measured the same
-    if (C.rr.on && mask == nullptr && fa.on) {
-      // b_1 = R (r - J x0) without J x0: the facet terms of x0 on every face,
-      // then the fused residual restriction (RRArgs) with level 1's pre-smoothing
-      launch_cg_facet_faces(c->cg, T, c->mgx, c->st, s);
-      if (!launch_mg_rrestrict(C.rr, c->st, c->r, c->mgx, cg_face_add_all(c->cg), C.b, C.dinv, C.omega, C.x, s))
-        return c->fail(TV_ERR_STATE, kRRChunkMsg);
-    } else if (fa.on && mg_restrict_folds_faces(C.xf) && n < kMgFoldFacesNodes) {
-      launch_cg_japply_partial(c->cg, T, c->mgx, c->w, c->st, s);
-      launch_mg_restrict(C.xf, c->st, c->r, c->w, &fa, mask, C.b, C.dinv, C.omega, C.x, s);
-    } else {
-      launch_cg_japply(c->cg, T, c->mgx, c->w, nullptr, nullptr, s, c->st);
-      launch_mg_restrict(C.xf, c->st, c->r, c->w, nullptr, mask, C.b, C.dinv, C.omega, C.x, s);
-    }
+    if (int e = mg_restrict_into(c, v, c->mg[0], mask, c->nT < kMgFoldFacesNodes)) return e;
     if (int e = mg_level(c, 1)) return e;
     mg_prolong_from(c, 0, c->mgx, mask);
   }
-  // J x, post-smoothing and (z.z, z.r) in the march epilogue (+ the side-face pass)
-  if (launch_cg_japply_post(c->cg, T, c->mgx, c->r, c->dinv, c->mg_omega0, c->z, c->st, c->partials, tail, s) >= 0)
-    return TV_OK;
-  launch_cg_japply_partial(c->cg, T, c->mgx, c->w, c->st, s);
-  launch_mg_post(n, c->st, c->mgx, c->r, c->w, &fa, c->dinv, c->mg_omega0, c->z, c->partials, tail, s);
+  mg_close0(c, v, tail);
   return TV_OK;
 }
 

@@ -271,18 +271,25 @@ VCYCLE_CASES = {
 VCYCLE_PARAMS = {"odd_graded_4_alpha": ("odd_graded_4", 0.37, 0.25)}
 
 
+# TVFEM_MG_RR per id; fused_restrict_coarse: into level 2 as well (bit 1), where level 1 -> 2 allows it
+# (plate_auto: 17 nodes along x, regular windows) and on the odd graded box
+VCYCLE_RR = {"jx_restrict": 0, "fused_restrict": 1, "fused_restrict_coarse": 3}
+VCYCLE_IDS = [(c, f) for c in list(VCYCLE_CASES) + list(VCYCLE_PARAMS) for f in ("jx_restrict", "fused_restrict")]
+VCYCLE_IDS += [(c, "fused_restrict_coarse") for c in ("plate_auto", "odd_graded_4")]
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("fused", [False, True], ids=["jx_restrict", "fused_restrict"])
-@pytest.mark.parametrize("case", list(VCYCLE_CASES) + list(VCYCLE_PARAMS))
+@pytest.mark.parametrize("case,fused", [pytest.param(c, f, id=f"{c}-{f}") for c, f in VCYCLE_IDS])
 def test_gmg_vcycle_operator_matches_numpy_restatement(case, fused, monkeypatch):
     """tv_precond_apply (one V-cycle: the PCApply of the solve) against the numpy
     V-cycle above at a non-uniform T, to 1e-11; the operator is symmetric (CG
-    needs it) and positive.  fused: level 0's restriction as the fused residual
-    restriction b_1 = R (r - J x0) without J x0 (k_mg_rrestrict, on by default
-    from 3M nodes; forced here, where the geometry allows it: thin_x_4 keeps the
-    J x path)"""
+    needs it) and positive.  fused_restrict: level 0's restriction as the fused
+    residual restriction b_1 = R (r - J x0) without J x0 (k_mg_rrestrict, on by
+    default from 3M nodes; forced here, where the geometry allows it: thin_x_4
+    keeps the J x path); fused_restrict_coarse: the restriction from level 1
+    into level 2 fused too (mg_level through the shared restriction step)"""
     torch = _torch()
-    monkeypatch.setenv("TVFEM_MG_RR", "1" if fused else "0")
+    monkeypatch.setenv("TVFEM_MG_RR", str(VCYCLE_RR[fused]))
     from tvfem import RectilinearMesh
     from tvfem.problem import ThermoViscoProblem
     mp = dict(O.MAIN_MODEL_PARAMS)
@@ -320,7 +327,7 @@ def test_gmg_vcycle_operator_matches_numpy_restatement(case, fused, monkeypatch)
     z_r, z_y = out
     e = relerr(z_r, B(r))
     sym = abs(y @ z_r - r @ z_y) / abs(y @ z_r)
-    print(f"[gmg] V-cycle {case} ({'fused' if fused else 'J x'} restriction): {nlev} levels, vs numpy {e:.2e}, "
+    print(f"[gmg] V-cycle {case} ({fused}): {nlev} levels, vs numpy {e:.2e}, "
           f"symmetry {sym:.1e}, r.Br {r @ z_r:.3e}")
     assert e < 1e-11, e
     assert sym < 1e-12, sym

@@ -114,6 +114,8 @@ def main():
                     help="write the five series (per-part directories) and check them against the gathered state")
     ap.add_argument("--mg-replicate", type=int, default=0,
                     help="GMG: coarse levels of at most this many nodes replicated (0: the library default)")
+    ap.add_argument("--dump", default=None, metavar="FILE",
+                    help="rank 0 saves the gathered T, phi, xi, sigma and the counts (npz): two library builds bit for bit")
     a = ap.parse_args()
     rank = int(os.environ["RANK"])
     world = int(os.environ["WORLD_SIZE"])
@@ -145,6 +147,7 @@ def main():
         ref, its_ref = run(mesh, 1, 0, steps, edit=a.edit, pc=a.pc, dirichlet=a.dirichlet, edit_field=a.edit_field,
                            family=a.family, dg_kernel=a.dg_kernel, edit_box=eb, paper=a.paper)
         res = {"comm": a.comm, "pcg": a.pcg, "pc": a.pc, "mesh": a.mesh, "its_parts": its, "its_single": its_ref}
+        dump = {"its_parts": np.array(its), "its_single": np.array(its_ref)}
         for k in ("T", "phi", "xi", "sigma"):
             if "l2g" in gathered[0]:  # scatter every part's owned vertices to their global ids
                 full = np.zeros_like(ref[k]).reshape(mesh.num_vertices, -1)
@@ -155,6 +158,7 @@ def main():
                 full = np.concatenate([np.asarray(g[k]) for g in gathered])
             e = np.linalg.norm(full - ref[k]) / np.linalg.norm(ref[k])
             res[k] = float(e)
+            dump[k] = full
             if a.output and k in ("T", "sigma"):  # every part's written series vs the gathered state
                 key = "outT" if k == "T" else "outS"
                 if "l2g_local" in gathered[0]:  # unstructured: the part's local vertices, ghosts included
@@ -170,6 +174,8 @@ def main():
                         o0 = int(g["goff0" if k == "T" else "goff1"][0]) * bs
                         errs.append(np.abs(wv - full[o0:o0 + wv.size]).max() if wv.size else 0.0)
                 res["output_" + k] = float(max(errs) / np.abs(full).max())
+        if a.dump:
+            np.savez(a.dump, **dump)
         print("PARTITION_CHECK " + json.dumps(res), flush=True)
     dist.barrier()
 
